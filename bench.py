@@ -7,7 +7,13 @@ are resident in HBM when the timed region starts: the closed loop feeds back xs[
 generated on the device.  Multi-GPU: one process per GPU, batch sharded by instance, no
 collective on the solve path (weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-per-gpu B] [--iters 3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-per-gpu B] [--iters 3] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds everything measured beside the headline:
+the measured FP64 peak, per-kernel times and rooflines, the CPU baseline, the return-set copy timed beside the region at N = 1 and the
+other single-GPU workloads (bench_side.py).  `--dump-outputs DIR` writes what the last timed step returned (the solution of a fixed, seeded
+sample of the instances and the next measured states) as DIR/<name>.npy, float64: two builds run with the same arguments can be compared
+output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process touches no GPU; it starts N fresh ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`), waits and relays rank 0's JSON line.  Under a launcher
@@ -32,6 +38,31 @@ from bench_common import both_bounds, cpu_baseline, f_ric, flop_counts, loop_str
 
 
 LINE_LIMIT = 3072  # bytes of the last stdout line (round 5's 24 KB line was not parsed by the driver)
+DUMP_SEED = 20240529     # --dump-outputs: the sample of instances / return rows is fixed by this seed and the batch size alone
+DUMP_INSTANCES = 1024    # instances of the handle's arrays written (Go2, H = 50: 33 KB each)
+DUMP_ROWS = 2048         # rows [x1 | u0 | K0] of the return set written (7.4 KB each)
+DUMP_LIMIT = 64 << 20    # bytes of one dump, all files
+
+
+def dump_sample(n, k):
+    """Sorted indices of a fixed, seeded choice of k of n items (all n if n <= k)."""
+    import numpy as np
+
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+
+
+def dump_outputs(d, arrays):
+    """arrays {name: array} -> d/<name>.npy, float64."""
+    import numpy as np
+
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def _r(v, n=5):
@@ -119,9 +150,13 @@ def main():
     ap.add_argument("--streams", type=int, default=1,
                     help="kinodynamics: run the iterations of N parts of the batch on N HIP streams (SMPC_STREAMS; tails of one part's "
                     "launches are filled by the next part's). Per-kernel rooflines then refer to launches of batch/N instances")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="skip the other single-GPU workloads measured beside the headline (profiling passes "
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline as well: FP64 peak, per-kernel times and rooflines, "
+                    "cpu_baseline, the return-set copy at N = 1, the other single-GPU workloads (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned to DIR/<name>.npy (float64; a fixed, "
+                    "seeded sample of the instances of the larger arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU legs")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the per-kernel times (and the side workloads)")
+    ap.add_argument("--headline-only", action="store_true", help="--full without the other single-GPU workloads measured beside the headline (profiling passes "
                     "whose per-kernel means must be those of the headline launches)")
     ap.add_argument("--sync-steps", action="store_true", help="host synchronisation after every control step (default: the closed loop is one in-order queue "
                     "on the handle's stream, synchronised only at the ends of the timed region)")
@@ -174,7 +209,8 @@ def main():
             g.build_emu()
         else:
             g.build_hip()
-            g.build_oracle()
+            if args.full or args.workload != "kinodynamics":
+                g.build_oracle()  # (the CPU legs)
     if dist is not None:
         dist.barrier()
     from simple_mpc import presets as P
@@ -184,6 +220,8 @@ def main():
     if args.workload != "kinodynamics":
         if world > 1 or dry:
             raise SystemExit("--workload %s is a single-GPU line" % args.workload)
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the headline (kinodynamics) workload only")
         import bench_side
 
         measure_fp64_peak()
@@ -200,7 +238,7 @@ def main():
         from simple_mpc._capi import SmpcLib
 
         lib = SmpcLib(g.EMU_LIB)
-    if rank == 0 and not dry:
+    if rank == 0 and not dry and args.full:
         measure_fp64_peak()
     gm, mh = make_mpc("kinodynamics", B, args.iters, local_rank, lib)
 
@@ -241,6 +279,7 @@ def main():
     row = gm.nx + gm.nu + gm.nu * gm.ndx
     gather_on = not args.no_gather and args.streams == 1
     gather_timed = gather_on and (world > 1 or args.gather or dry)
+    gather_on = gather_timed or (gather_on and args.full)  # (N = 1: the copy measured beside the timed region is a --full figure)
     g_events = []
     if gather_on and not dry:
         main_s = torch.cuda.ExternalStream(gm.stream(), device=dev)
@@ -304,7 +343,7 @@ def main():
                     sys.exit(3)
                 gather_error = repr(exc)
                 gather_on = gather_timed = False
-    profile = not args.no_profile and not dry
+    profile = args.full and not args.no_profile and not dry
     if profile:
         gm.set_profiling(True)
         gm.reset_kernel_times()
@@ -321,6 +360,19 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     kt = gm.kernel_times() if profile else {}
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step, for a fixed sample of rank 0's instances: the solution (xs, us, K0),
+        # the solver scalars, the next measured states (xs[1] + noise, fed back); with the return set inside the timed region, a sample of
+        # the rows rank 0 received
+        pick = dump_sample(B, DUMP_INSTANCES)
+        outs = {"xs": gm.xs[pick], "us": gm.us[pick], "K0": gm.K0[pick], "info": gm.info[pick], "x_meas": (Xh if dry else X.cpu().numpy())[pick]}
+        if gather_timed:
+            if dry:
+                rows = (torch.stack(gathered_h) if dist is not None else torch.from_numpy(pack_h)).reshape(-1, row).numpy()
+            else:
+                rows = pinned[(step_no[0] - 1) & 1].numpy()
+            outs["return_rows"] = rows[dump_sample(len(rows), DUMP_ROWS)]
+        dump_outputs(args.dump_outputs, outs)
     dt_with_gather = None
     if gather_on and not gather_timed:
         # N = 1: the same closed loop with the return set moved to the pinned buffer every step, measured beside the timed region
@@ -423,7 +475,7 @@ def main():
                 # GPU with other launches, so only the whole-step figure is meaningful in this mode
                 out["roofline"] = dict(out["step_roofline"], kernel="whole control step (--streams %d: per-kernel durations overlap)" % args.streams, traffic=None)
                 del out["kernel_share"]
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if world == 1 and args.full and not args.no_cpu_baseline and not dry:
             out["cpu_baseline"] = cpu_baseline(args.iters)
         if world == 1 and profile and not args.headline_only:
             # the other single-GPU BASELINE configurations, measured briefly beside the headline (not part of `value`): bench_side.py.  Their full

@@ -36,6 +36,25 @@ def test_gpus_flag_starts_that_many_ranks(built):
     assert g["in_timed_region"] is True and "error" not in g and g["rows_ok"] is True
 
 
+def test_dump_outputs_are_the_same_from_run_to_run(built, tmp_path):
+    """--dump-outputs writes the last timed step's outputs, float64; the same arguments give the same inputs, hence the same files (the
+    2-rank rehearsal also writes the return-set rows rank 0 received)."""
+    import numpy as np
+
+    dumps = []
+    for d in ("a", "b"):
+        o = _run(["--gpus", "2", "--dump-outputs", str(tmp_path / d)])
+        assert o["steps"] == 2 and "cpu_baseline" not in o and "kernel_ms" not in o  # (a plain run: the timed steps only)
+        dumps.append({f[:-4]: np.load(str(tmp_path / d / f)) for f in sorted(os.listdir(str(tmp_path / d)))})
+    a, b = dumps
+    assert sorted(a) == ["K0", "info", "return_rows", "us", "x_meas", "xs"]
+    assert a["xs"].shape == (2, 51, 37) and a["us"].shape == (2, 50, 24) and a["x_meas"].shape == (2, 37) and a["return_rows"].shape == (4, 925)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float64 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_default_batch_is_the_baseline_configuration():
     sys.path.insert(0, ROOT)
     src = open(os.path.join(ROOT, "bench.py")).read()

@@ -96,7 +96,7 @@ def test_emu_dense_weights_and_com_reference(lib):
     _run_pair(om, gm, rb, 2, 4, 1e-9)
 
 
-def test_emu_standing_and_lane_order(lib):
+def test_emu_standing_and_lane_order(lib, tmp_path):
     om, gm, rb = S.make_cent_pair(2, 1, lib=lib)
     om.switchToStand()
     gm.switchToStand()
@@ -110,7 +110,7 @@ def test_emu_standing_and_lane_order(lib):
     )
     outs = []
     for rev in ("0", "1"):
-        path = "/tmp/smpc_cent_order_%s.npy" % rev
+        path = str(tmp_path / ("order_%s.npy" % rev))
         subprocess.check_call([sys.executable, "-c", code, path], env=dict(os.environ, SMPC_EMU_REVERSE=rev))
         outs.append(np.load(path))
     assert np.array_equal(outs[0], outs[1]), "a missing phase barrier makes the result depend on the lane order"

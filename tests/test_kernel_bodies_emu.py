@@ -155,7 +155,7 @@ def test_line_search_backtracking_matches(lib):
     assert seen_backtrack, "scenario no longer exercises backtracking"
 
 
-def test_dense_and_structured_riccati_agree(built):
+def test_dense_and_structured_riccati_agree(built, tmp_path):
     """The model-independent dense sweep (SMPC_RICCATI=dense) and the kinodynamics-structured sweep solve the same
     KKT system: identical trajectories up to round-off."""
     code = (
@@ -170,7 +170,7 @@ def test_dense_and_structured_riccati_agree(built):
     )
     outs = []
     for mode in ("dense", "kino"):
-        path = "/tmp/smpc_emu_riccati_%s.npz" % mode
+        path = str(tmp_path / ("riccati_%s.npz" % mode))
         env = dict(os.environ, SMPC_RICCATI=mode)
         subprocess.check_call([sys.executable, "-c", code, path], env=env)
         outs.append(np.load(path))
@@ -178,7 +178,7 @@ def test_dense_and_structured_riccati_agree(built):
     assert S.rel_err(outs[0]["K0"], outs[1]["K0"]) < 1e-6
 
 
-def test_speculative_line_search_is_the_sequential_algorithm(built):
+def test_speculative_line_search_is_the_sequential_algorithm(built, tmp_path):
     """Tentative full step + next derivative pass as the alpha = 1 trial (run_iterations) against explicit trial
     evaluations in every iteration (SMPC_NO_SPECULATIVE_LS): bit-identical iterates, on a scenario that rejects alpha = 1
     in early and late iterations (restore / backtrack / re-derive path)."""
@@ -195,7 +195,7 @@ def test_speculative_line_search_is_the_sequential_algorithm(built):
     )
     outs = []
     for mode in ("spec", "seq"):
-        path = "/tmp/smpc_emu_ls_%s.npz" % mode
+        path = str(tmp_path / ("ls_%s.npz" % mode))
         env = dict(os.environ)
         env.pop("SMPC_NO_SPECULATIVE_LS", None)
         if mode == "seq":
@@ -220,7 +220,7 @@ def test_batch_instances_are_independent(lib):
     assert np.array_equal(gm4.xs[2], gm1.xs[0])
 
 
-def test_lane_order_independence(built):
+def test_lane_order_independence(built, tmp_path):
     """Run the same closed loop with lanes executed in descending order: a missing phase barrier (a lane
     reading what a later lane writes in the same phase) changes the result in one of the two orders."""
     code = (
@@ -235,7 +235,7 @@ def test_lane_order_independence(built):
     )
     outs = []
     for rev in ("0", "1"):
-        path = "/tmp/smpc_emu_order_%s.npy" % rev
+        path = str(tmp_path / ("order_%s.npy" % rev))
         env = dict(os.environ, SMPC_EMU_REVERSE=rev)
         subprocess.check_call([sys.executable, "-c", code, path], env=env)
         outs.append(np.load(path))

@@ -33,7 +33,7 @@ for k, d in res.items():
             if c.startswith("SQ_INSTS_") and "/" not in c:
                 o[c + "_per_wave"] = o[c] / o["SQ_WAVES"]
     out[k] = o
-json.dump({"source": "rocprofv3 --kernel-trace --pmc <SQ counters> (own passes, no other trace domain) -- python3 bench.py --steps 2 --warmup 1 "
+json.dump({"source": "rocprofv3 --kernel-trace --pmc <SQ counters> (own passes, no other trace domain) -- python3 bench.py --full --steps 2 --warmup 1 "
            "--no-cpu-baseline; averages over the full-batch launches (B = 4096) of the main kernel symbols; raw counter sums over all "
            "shader engines / XCDs, ratios as named", "kernels": out}, open(sys.argv[1], "w"), indent=1)
 for k, o in out.items():

@@ -14,10 +14,10 @@ ROOT=$PWD # (the program is named by an absolute path: rocprofv3 runs from /tmp)
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT/prof_$TAG"
 export TMPDIR=/tmp
-BENCH="bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+BENCH="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
 
 [ -x tools/micro/fp64_peak.bin ] && ./tools/micro/fp64_peak.bin 1.0 > "$OUT/${TAG}_fp64_peak.json"
-python3 bench.py > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" || echo "bench failed"
+python3 bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" || echo "bench failed"
 tail -1 "$OUT/${TAG}_bench.json" | cut -c1-300
 cp bench_full.json "$OUT/${TAG}_bench_full.json" 2> /dev/null # (everything the run measured; the printed line is the compact object)
 cp bench_side.json "$OUT/${TAG}_bench_side.json" 2> /dev/null
@@ -26,12 +26,12 @@ python3 bench.py --workload centroidal > "$OUT/${TAG}_bench_centroidal.json" 2>>
 run_prof() { # name, rocprofv3 options...
   local name=$1
   shift
-  (cd /tmp && rocprofv3 "$@" --output-format csv -d "$OUT/prof_$TAG/$name" -o "$name" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/prof_$TAG/$name.log" 2>&1) || echo "$name failed"
+  (cd /tmp && rocprofv3 "$@" --output-format csv -d "$OUT/prof_$TAG/$name" -o "$name" -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/prof_$TAG/$name.log" 2>&1) || echo "$name failed"
 }
 run_prof stats --kernel-trace --stats
 # the headline workload alone (its kernel symbols are shared with the side workloads -- control stack at k = 1, standing robots --, whose
 # launches would shift the per-kernel means the bench line's HIP-event averages are checked against)
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG/headline" -o headline -- python3 "$ROOT/bench.py" --steps 8 --warmup 2 --no-cpu-baseline --headline-only > "$OUT/prof_$TAG/headline.log" 2>&1) || echo "headline failed"
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG/headline" -o headline -- python3 "$ROOT/bench.py" --full --steps 8 --warmup 2 --no-cpu-baseline --headline-only > "$OUT/prof_$TAG/headline.log" 2>&1) || echo "headline failed"
 run_prof fetch --kernel-trace --pmc FETCH_SIZE
 run_prof write --kernel-trace --pmc WRITE_SIZE
 run_prof sq1 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_F64 SQ_WAIT_ANY SQ_WAIT_INST_ANY
