@@ -308,17 +308,30 @@ namespace simple_mpc
     std::vector<int> getFootLandCycle(const std::string & ee) { return timing(ee, 1); }
     smpc_handle * handle() { return h_; }
 
-    // reference src/mpc.cpp:346-352, t = 0 or 1: [B][dim] with dim = 2 nv (kinodynamics) or 9 (centroidal)
+    // reference src/mpc.cpp:346-352: [B][dim] with dim = 2 nv (kinodynamics, full dynamics) or 9 (centroidal).  t = 0, 1 are kept by the
+    // solver; 2 <= t < H need setRetainStateDerivatives(true) before the control step
     std::vector<double> getStateDerivative(int t)
     {
-      if (t != 0 && t != 1)
-        throw std::runtime_error("state derivative is retained for t = 0, 1 only");
-      const int dim = nx() == 9 ? 9 : 2 * dims_[1];
-      std::vector<double> all((size_t)batch_ * 2 * dim), out((size_t)batch_ * dim);
-      check(smpc_get_state_derivative01(h_, all.data()));
+      const int dim = nx() == 9 ? 9 : 2 * dims_[1], H = dims_[7];
+      if (t < 0 || t >= H)
+        throw std::runtime_error("Stage index exceeds stage vector size");
+      const bool first2 = t == 0 || t == 1;
+      const int nt = first2 ? 2 : H;
+      std::vector<double> all((size_t)batch_ * nt * dim), out((size_t)batch_ * dim);
+      check(first2 ? smpc_get_state_derivative01(h_, all.data()) : smpc_get_state_derivatives(h_, all.data()));
       for (int b = 0; b < batch_; b++)
         for (int i = 0; i < dim; i++)
-          out[(size_t)b * dim + i] = all[((size_t)b * 2 + t) * dim + i];
+          out[(size_t)b * dim + i] = all[((size_t)b * nt + t) * dim + i];
+      return out;
+    }
+    // retain the state derivatives of every stage (one more kernel per control step; off by default)
+    void setRetainStateDerivatives(bool on) { check(smpc_set_retain_state_derivatives(h_, on ? 1 : 0)); }
+    // [B][H][dim] of the last control step
+    std::vector<double> getStateDerivatives()
+    {
+      const int dim = nx() == 9 ? 9 : 2 * dims_[1];
+      std::vector<double> out((size_t)batch_ * dims_[7] * dim);
+      check(smpc_get_state_derivatives(h_, out.data()));
       return out;
     }
 

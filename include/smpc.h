@@ -262,6 +262,20 @@ int smpc_debug_get_extra_multipliers(smpc_handle * h, int which, double * out);
 int smpc_get_lams(smpc_handle * h, double * out);
 /* MPC::getStateDerivative(t) for t = 0,1 (reference src/mpc.cpp:346-352). out: [B][2][2 nv] */
 int smpc_get_state_derivative01(smpc_handle * h, double * out);
+/* MPC::getStateDerivative(t) for EVERY stage t (reference src/mpc.cpp:346-352: Et.ev[t].xdot of the accepted iterate).
+ * Opt-in per handle: with the switch on, every control step (smpc_iterate, smpc_iterate_device, smpc_iterate_async) enqueues one more
+ * kernel on the handle's stream after the solve, which evaluates the continuous dynamics of every (instance, stage) at the returned
+ * xs[t], us[t] with the stage's contact mask and parameters; off (the default), nothing is launched or allocated.
+ *   smpc_set_retain_state_derivatives   on = 1 allocates [B][H][dim] doubles on the first enable (SMPC_ERR_RUNTIME if that fails;
+ *                                       the handle stays usable); on = 0 stops the launches
+ *   smpc_get_state_derivatives          out [B][H][dim] (host); dim = 2 nv (kinodynamics, full dynamics), 9 (centroidal)
+ *   smpc_get_state_derivatives_device   the same into a device buffer, asynchronous on the handle's stream
+ * The getters return SMPC_ERR_INVALID when the switch is off, when no iterate has run since it was enabled, and after smpc_load_state
+ * until the next iterate (the buffer is not part of the checkpoint: smpc_state_size does not change).  Stages 0, 1 equal
+ * smpc_get_state_derivative01. */
+int smpc_set_retain_state_derivatives(smpc_handle * h, int on);
+int smpc_get_state_derivatives(smpc_handle * h, double * out);
+int smpc_get_state_derivatives_device(smpc_handle * h, double * out_device);
 /* MPC::getReferencePose(t, foot).translation() for all t, feet (reference src/mpc.cpp:336-339). out: [B][H][nfeet][3] */
 int smpc_get_reference_poses(smpc_handle * h, double * out);
 /* MPC::foot_takeoff_times_ / foot_land_times_ (reference include/simple-mpc/mpc.hpp:184-185). which: 0 takeoff, 1 land.

@@ -29,6 +29,33 @@ struct smpc_handle
   std::unique_ptr<KinoEngine<DimsGo2>> eng;
   std::unique_ptr<CentEngineBase> cent; // centroidal handle (smpc_create_centroidal): eng is null
   std::unique_ptr<FullEngineBase> full; // full-dynamics handle (smpc_create_fulldynamics): eng and cent are null
+  // state derivatives of every stage (smpc_set_retain_state_derivatives): [B][H][dim] on the handle's device, allocated on the first enable
+  double * xdot_all = nullptr;
+  bool retain_xdot = false;
+  enum
+  {
+    XDOT_NONE,  // no iterate since the switch was enabled
+    XDOT_VALID, // filled by the last iterate
+    XDOT_STALE  // smpc_load_state since the last iterate (the buffer is not part of the checkpoint)
+  } xdot_state = XDOT_NONE;
+  int device() const { return full ? full->device_id : (cent ? cent->device_id : eng->device_id); }
+  stream_t stream() const { return full ? full->stream : (cent ? cent->stream : eng->stream); }
+  size_t xdot_doubles() const
+  {
+    if (full)
+      return (size_t)full->B * full->H * 2 * full->dims[1];
+    if (cent)
+      return (size_t)cent->B * cent->H * 9;
+    return (size_t)eng->B * eng->H * 2 * DimsGo2::NV;
+  }
+  ~smpc_handle()
+  {
+    if (xdot_all)
+    {
+      set_device(device());
+      dev_free(xdot_all);
+    }
+  }
 };
 
 namespace
@@ -68,6 +95,32 @@ namespace
     return ms;
   }
   const char * KINO_ONLY = "this entry point needs a kinodynamics handle (smpc_create)";
+  // one control step has been enqueued: with retention on, the state derivatives of every stage at its iterate (one launch on the stream)
+  void retain_after_iterate(smpc_handle * h)
+  {
+    if (!h->retain_xdot)
+      return;
+    if (h->full)
+      h->full->state_derivatives(h->xdot_all);
+    else if (h->cent)
+      h->cent->state_derivatives(h->xdot_all);
+    else
+      h->eng->state_derivatives(h->xdot_all);
+    h->xdot_state = smpc_handle::XDOT_VALID;
+  }
+  // why the retained state derivatives cannot be read, or null
+  const char * xdot_refusal(const smpc_handle * h)
+  {
+    if (!h->retain_xdot)
+      return "state derivatives of stages t >= 2 are not retained: enable smpc_set_retain_state_derivatives(h, 1) (Python: "
+             "setRetainStateDerivatives(True)) before iterate";
+    if (h->xdot_state == smpc_handle::XDOT_NONE)
+      return "no iterate has run since smpc_set_retain_state_derivatives enabled retention: run iterate first";
+    if (h->xdot_state == smpc_handle::XDOT_STALE)
+      return "smpc_load_state has run since the last iterate: the state derivatives retained by smpc_set_retain_state_derivatives are "
+             "not part of the checkpoint; run iterate first";
+    return nullptr;
+  }
 } // namespace
 
 extern "C"
@@ -541,21 +594,53 @@ extern "C"
   {
     if (!h || !X)
       return fail(SMPC_ERR_INVALID, "null argument");
+    h->xdot_state = smpc_handle::XDOT_NONE;
     if (h->full)
-      return guarded([&] { h->full->iterate_host(X); });
+      return guarded([&] {
+        h->full->iterate_host(X);
+        if (h->retain_xdot)
+        {
+          retain_after_iterate(h);
+          h->full->sync();
+        }
+      });
     if (h->cent)
-      return guarded([&] { h->cent->iterate_host(X); });
-    return guarded([&] { h->eng->iterate_host(X); });
+      return guarded([&] {
+        h->cent->iterate_host(X);
+        if (h->retain_xdot)
+        {
+          retain_after_iterate(h);
+          h->cent->sync();
+        }
+      });
+    return guarded([&] {
+      h->eng->iterate_host(X);
+      if (h->retain_xdot)
+      {
+        retain_after_iterate(h);
+        h->eng->sync();
+      }
+    });
   }
   int smpc_iterate_async(smpc_handle * h, const double * X)
   {
     if (!h || !X)
       return fail(SMPC_ERR_INVALID, "null argument");
+    h->xdot_state = smpc_handle::XDOT_NONE;
     if (h->full)
-      return guarded([&] { h->full->iterate_host(X); }); // (synchronous on these handles)
+      return guarded([&] {
+        h->full->iterate_host(X); // (synchronous on these handles)
+        retain_after_iterate(h);
+      });
     if (h->cent)
-      return guarded([&] { h->cent->iterate_host(X); });
-    return guarded([&] { h->eng->iterate_host_async(X); });
+      return guarded([&] {
+        h->cent->iterate_host(X);
+        retain_after_iterate(h);
+      });
+    return guarded([&] {
+      h->eng->iterate_host_async(X);
+      retain_after_iterate(h);
+    });
   }
   int smpc_gather_outputs(smpc_handle * h, double * out, size_t row_doubles)
   {
@@ -587,11 +672,21 @@ extern "C"
   {
     if (!h || !Xd)
       return fail(SMPC_ERR_INVALID, "null argument");
+    h->xdot_state = smpc_handle::XDOT_NONE;
     if (h->full)
-      return guarded([&] { h->full->iterate_device(Xd); });
+      return guarded([&] {
+        h->full->iterate_device(Xd);
+        retain_after_iterate(h);
+      });
     if (h->cent)
-      return guarded([&] { h->cent->iterate_device(Xd); });
-    return guarded([&] { h->eng->iterate_device(Xd); });
+      return guarded([&] {
+        h->cent->iterate_device(Xd);
+        retain_after_iterate(h);
+      });
+    return guarded([&] {
+      h->eng->iterate_device(Xd);
+      retain_after_iterate(h);
+    });
   }
   int smpc_wait(smpc_handle * h)
   {
@@ -644,6 +739,8 @@ extern "C"
   {
     if (!h || !buffer)
       return fail(SMPC_ERR_INVALID, "null argument");
+    if (h->xdot_state == smpc_handle::XDOT_VALID)
+      h->xdot_state = smpc_handle::XDOT_STALE;
     return guarded([&] { state_pass(h, StateIO::LOAD, const_cast<void *>(buffer), size); });
   }
   int smpc_get_x_device(smpc_handle * h, int t, double * out_device)
@@ -741,6 +838,59 @@ extern "C"
     if (h->cent)
       return guarded([&] { h->cent->get_linear(h->cent->bufs().xdot01, (size_t)h->cent->B * 18, out); });
     return guarded([&] { h->eng->get_linear(h->eng->buf.xdot01, (size_t)h->eng->B * 4 * DimsGo2::NV, out); });
+  }
+  int smpc_set_retain_state_derivatives(smpc_handle * h, int on)
+  {
+    if (!h)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!on)
+    {
+      h->retain_xdot = false;
+      h->xdot_state = smpc_handle::XDOT_NONE;
+      return SMPC_OK;
+    }
+    if (h->retain_xdot)
+      return SMPC_OK;
+    if (!h->xdot_all)
+    {
+      try
+      {
+        set_device(h->device());
+        h->xdot_all = (double *)dev_alloc(h->xdot_doubles() * sizeof(double));
+      }
+      catch (const std::exception & e)
+      {
+        dev_clear_error(); // (the handle stays usable, retention stays off)
+        return fail(SMPC_ERR_RUNTIME, std::string("smpc_set_retain_state_derivatives: ") + e.what());
+      }
+    }
+    h->retain_xdot = true;
+    h->xdot_state = smpc_handle::XDOT_NONE;
+    return SMPC_OK;
+  }
+  int smpc_get_state_derivatives(smpc_handle * h, double * out)
+  {
+    if (!h || !out)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (const char * why = xdot_refusal(h))
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      set_device(h->device());
+      stream_sync(h->stream());
+      d2h(out, h->xdot_all, h->xdot_doubles() * sizeof(double), h->stream());
+      stream_sync(h->stream());
+    });
+  }
+  int smpc_get_state_derivatives_device(smpc_handle * h, double * out_device)
+  {
+    if (!h || !out_device)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (const char * why = xdot_refusal(h))
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      set_device(h->device());
+      d2d(out_device, h->xdot_all, h->xdot_doubles() * sizeof(double), h->stream());
+    });
   }
   int smpc_get_reference_poses(smpc_handle * h, double * out)
   {

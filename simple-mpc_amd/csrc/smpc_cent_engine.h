@@ -99,6 +99,7 @@ namespace smpc
     virtual void interpolate(double delay, int knots, const double * X_meas, double * x_out, double * xdot_out, double * f_out, double * u_out) = 0;
     virtual size_t state_io(StateIO & io) = 0;
     virtual void get_K(double * out, bool all) = 0;
+    virtual void state_derivatives(double * out) = 0; // xdot of every stage at the last solve's iterate, [B][H][9] (device, handle's stream)
     void get_ring(const double * src, int n, int count, double * out)
     {
       set_device(device_id);
@@ -940,6 +941,15 @@ namespace smpc
       h2d(X_dev, X, (size_t)B * DK::NX * sizeof(double), stream);
       iterate_device(X_dev);
       stream_sync(stream);
+    }
+    void state_derivatives(double * out) override
+    {
+      set_device(device_id);
+      XdotArgs<CentBuffers<DC>> a;
+      a.b = buf;
+      a.head = head;
+      a.out = out;
+      launch<XdotArgs<CentBuffers<DC>>, xdot_all_body<DC, CentBuffers<DC>, XD_CENT>, 64>(xdot_grid(XD_CENT, B, H), stream, a);
     }
     void sync() override
     {

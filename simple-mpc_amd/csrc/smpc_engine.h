@@ -22,6 +22,7 @@
 #include "smpc_kino_deriv2.h"
 #include "smpc_solver_kernels.h"
 #include "smpc_full_kernels.h"
+#include "smpc_xdot.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -1353,6 +1354,21 @@ namespace smpc
         upload_stages();
       stream_sync(stream);
       return io.pos;
+    }
+    // xdot of every stage at the iterate of the last solve, out [B][H][2 NV] (device): one launch on the handle's stream (smpc_xdot.h)
+    void state_derivatives(double * out)
+    {
+      set_device(device_id);
+      XdotArgs<Buffers<D>> a;
+      a.b = buf;
+      a.head = head;
+      a.out = out;
+      if (lane_slots == 1)
+        launch<XdotArgs<Buffers<D>>, xdot_all_body<D, Buffers<D>, XD_KINO_LANE, 1>, 64>(xdot_grid(XD_KINO_LANE, B, H), stream, a);
+      else if (lane_slots == 2)
+        launch<XdotArgs<Buffers<D>>, xdot_all_body<D, Buffers<D>, XD_KINO_LANE, 2>, 64>(xdot_grid(XD_KINO_LANE, B, H), stream, a);
+      else
+        launch<XdotArgs<Buffers<D>>, xdot_all_body<D, Buffers<D>, XD_KINO_WAVE>, 64>(xdot_grid(XD_KINO_WAVE, B, H), stream, a);
     }
     void iterate_host(const double * X)
     {

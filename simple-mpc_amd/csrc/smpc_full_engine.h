@@ -72,6 +72,7 @@ namespace smpc
     virtual void sim_step_device(double * X_dev, const double * tau_dev, unsigned mask, const double * Kp, const double * Kd, double dt) = 0;
     virtual void wait_stream(stream_t other) = 0;
     virtual void riccati_feedback(double delay, const double * X, double * u_out) = 0;
+    virtual void state_derivatives(double * out) = 0; // xdot of every stage at the last solve's iterate, [B][H][2 NV] (device, handle's stream)
   };
 
   template <class D>
@@ -770,6 +771,15 @@ namespace smpc
       h2d(X_dev, X, (size_t)B * D::NX * sizeof(double), stream);
       iterate_device(X_dev);
       stream_sync(stream);
+    }
+    void state_derivatives(double * out) override
+    {
+      set_device(device_id);
+      XdotArgs<Buffers<D>> a;
+      a.b = buf;
+      a.head = head;
+      a.out = out;
+      launch<XdotArgs<Buffers<D>>, xdot_all_body<D, Buffers<D>, XD_FULL>, 64>(xdot_grid(XD_FULL, B, H), stream, a);
     }
     void sync() override
     {

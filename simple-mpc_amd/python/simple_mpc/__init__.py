@@ -886,9 +886,26 @@ class BatchedMPC:
         return out
 
     def getStateDerivative(self, t):
-        if t not in (0, 1):
-            raise RuntimeError("state derivative is retained for t = 0, 1 only")
-        return self._get("smpc_get_state_derivative01", (self.B, 2, self.ocp_handler._xdot_size()))[:, t, :]
+        """MPC::getStateDerivative(t) (reference src/mpc.cpp:346-352), [B, dim].  t = 0, 1 are kept by the solver; 2 <= t < H need
+        setRetainStateDerivatives(True) before the control step."""
+        if t in (0, 1):
+            return self._get("smpc_get_state_derivative01", (self.B, 2, self.ocp_handler._xdot_size()))[:, t, :]
+        if not isinstance(t, (int, np.integer)) or t < 0 or t >= self.H:
+            raise RuntimeError("Stage index exceeds stage vector size")
+        return self.getStateDerivatives()[:, t, :]
+
+    def setRetainStateDerivatives(self, on=True):
+        """Retain the state derivatives of every stage: each control step then enqueues one more kernel that evaluates the dynamics
+        of every (instance, stage) at the returned iterate (smpc_set_retain_state_derivatives).  Off by default."""
+        self._lib.check(self._lib.L.smpc_set_retain_state_derivatives(self._h, int(bool(on))))
+
+    def getStateDerivatives(self):
+        """State derivatives of every stage of the last control step, [B, H, dim] (needs setRetainStateDerivatives(True))."""
+        return self._get("smpc_get_state_derivatives", (self.B, self.H, self.ocp_handler._xdot_size()))
+
+    def get_state_derivatives_device(self, device_ptr):
+        """The same into a device buffer [B][H][dim] (asynchronous on the handle's stream)."""
+        self._lib.check(self._lib.L.smpc_get_state_derivatives_device(self._h, C.c_void_p(int(device_ptr))))
 
     def getReferencePoses(self):
         return self._get("smpc_get_reference_poses", (self.B, self.H, self.nf, 3))

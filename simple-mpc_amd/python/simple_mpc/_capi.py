@@ -152,7 +152,8 @@ SYMBOLS = [
     "smpc_generate_cycle_horizon", "smpc_switch_to_walk", "smpc_switch_to_stand", "smpc_set_velocity_base_batched", "smpc_set_stage_reference", "smpc_get_stage_reference", "smpc_set_reference_pose",
     "smpc_get_reference_pose", "smpc_set_reference_pose_se3", "smpc_get_reference_pose_se3", "smpc_get_contact_state", "smpc_get_cycling_contact_state", "smpc_debug_get_extra_multipliers", "smpc_set_x_reference",
     "smpc_state_size", "smpc_save_state", "smpc_load_state", "smpc_iterate", "smpc_iterate_device", "smpc_wait", "smpc_get_stream", "smpc_get_x_device", "smpc_get_xs", "smpc_get_us", "smpc_get_K0", "smpc_get_Ks",
-    "smpc_get_vs", "smpc_get_lams", "smpc_get_state_derivative01", "smpc_get_reference_poses",
+    "smpc_get_vs", "smpc_get_lams", "smpc_get_state_derivative01", "smpc_set_retain_state_derivatives", "smpc_get_state_derivatives",
+    "smpc_get_state_derivatives_device", "smpc_get_reference_poses",
     "smpc_set_early_exit_on_tol", "smpc_iterate_async", "smpc_gather_outputs", "smpc_gather_outputs_device", "smpc_gather_outputs_peer", "smpc_get_foot_timing", "smpc_get_info", "smpc_get_status", "smpc_get_cold_trace", "smpc_lq_size", "smpc_debug_get_lq",
     "smpc_debug_get_steps", "smpc_debug_get_terminal", "smpc_debug_get_phase_cycles", "smpc_set_profiling", "smpc_get_kernel_times", "smpc_get_kernel_times_n", "smpc_kernel_time_slots", "smpc_reset_kernel_times",
     "smpc_interpolate", "smpc_interpolate_knots", "smpc_friction_compensation", "smpc_update_internal_data", "smpc_full_forward_dynamics", "smpc_centroidal_dynamics", "smpc_riccati_feedback",
@@ -252,6 +253,9 @@ class SmpcLib:
         L.smpc_get_x_device.argtypes = [vp, C.c_int, vp]
         for nm in ("xs", "us", "K0", "Ks", "vs", "lams", "state_derivative01", "reference_poses", "info"):
             getattr(L, "smpc_get_" + nm).argtypes = [vp, _dp]
+        L.smpc_set_retain_state_derivatives.argtypes = [vp, C.c_int]
+        L.smpc_get_state_derivatives.argtypes = [vp, _dp]
+        L.smpc_get_state_derivatives_device.argtypes = [vp, vp]
         L.smpc_get_foot_timing.argtypes = [vp, C.c_int, C.c_int, _ip, C.c_int]
         L.smpc_get_cold_trace.argtypes = [vp, _dp, C.c_int]
         L.smpc_lq_size.argtypes = [vp]
