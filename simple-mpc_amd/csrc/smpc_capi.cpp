@@ -1,5 +1,6 @@
-// smpc_capi.cpp -- extern "C" entry points of include/smpc.h over KinoEngine.  Compiled by hipcc for
-// gfx950 (kernels are instantiated here); there is no CPU implementation behind these symbols.
+// smpc_capi.cpp -- extern "C" entry points of include/smpc.h.  An smpc_handle holds one MpcEngineBase (smpc_engine_base.h): every MPC entry
+// point checks its arguments and makes one call through that interface; the concrete engines are named in the create functions only.
+// Compiled by hipcc for gfx950 (kernels are instantiated here); there is no CPU implementation behind these symbols.
 #include "../../include/smpc.h"
 #include "../../include/smpc_robots_builtin.h"
 #include "smpc_cent_engine.h"
@@ -26,9 +27,7 @@ typedef FullDims<23, 2, 6, 0, 0, 1> KinoTalos;  // KINODYNAMICS OCP of the Talos
 
 struct smpc_handle
 {
-  std::unique_ptr<KinoEngine<DimsGo2>> eng;
-  std::unique_ptr<CentEngineBase> cent; // centroidal handle (smpc_create_centroidal): eng is null
-  std::unique_ptr<FullEngineBase> full; // full-dynamics handle (smpc_create_fulldynamics): eng and cent are null
+  std::unique_ptr<MpcEngineBase> e; // kinodynamics (smpc_create), centroidal (smpc_create_centroidal) or full dynamics (smpc_create_fulldynamics)
   // state derivatives of every stage (smpc_set_retain_state_derivatives): [B][H][dim] on the handle's device, allocated on the first enable
   double * xdot_all = nullptr;
   bool retain_xdot = false;
@@ -38,21 +37,11 @@ struct smpc_handle
     XDOT_VALID, // filled by the last iterate
     XDOT_STALE  // smpc_load_state since the last iterate (the buffer is not part of the checkpoint)
   } xdot_state = XDOT_NONE;
-  int device() const { return full ? full->device_id : (cent ? cent->device_id : eng->device_id); }
-  stream_t stream() const { return full ? full->stream : (cent ? cent->stream : eng->stream); }
-  size_t xdot_doubles() const
-  {
-    if (full)
-      return (size_t)full->B * full->H * 2 * full->dims[1];
-    if (cent)
-      return (size_t)cent->B * cent->H * 9;
-    return (size_t)eng->B * eng->H * 2 * DimsGo2::NV;
-  }
   ~smpc_handle()
   {
     if (xdot_all)
     {
-      set_device(device());
+      set_device(e->device_id);
       dev_free(xdot_all);
     }
   }
@@ -74,10 +63,24 @@ namespace
       f();
       return SMPC_OK;
     }
+    catch (const InvalidCall & e) // (not on this handle kind, or an index out of its range: smpc_engine_base.h)
+    {
+      return fail(SMPC_ERR_INVALID, e.what());
+    }
     catch (const std::exception & e)
     {
       return fail(SMPC_ERR_RUNTIME, e.what());
     }
+  }
+  // the engine of a freshly built handle -> *out
+  template <class F>
+  int create_handle(smpc_handle ** out, F && make)
+  {
+    return guarded([&] {
+      std::unique_ptr<smpc_handle> h(new smpc_handle());
+      h->e.reset(make());
+      *out = h.release();
+    });
   }
   HostMpcSettings host_mpc(const smpc_mpc_settings * mpc)
   {
@@ -94,18 +97,58 @@ namespace
     ms.T = mpc->T;
     return ms;
   }
-  const char * KINO_ONLY = "this entry point needs a kinodynamics handle (smpc_create)";
+  // the weights enter the Gauss-Newton Hessian as they are: they must be symmetric
+  bool symmetric(const std::vector<double> & w, int n)
+  {
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < i; j++)
+        if (std::fabs(w[(size_t)i * n + j] - w[(size_t)j * n + i]) > 1e-12 * (1.0 + std::fabs(w[(size_t)i * n + j])))
+          return false;
+    return true;
+  }
+  // what the settings of the dense engine's two problems (full dynamics; kinodynamics with 6-D feet) share; nu = size of the control,
+  // na = number of actuated joints
+  template <class S>
+  HostFullSettings host_full(const S * ocp, int ndx, int nu, int na, int fs)
+  {
+    HostFullSettings s;
+    s.timestep = ocp->timestep;
+    s.w_x.assign(ocp->w_x, ocp->w_x + (size_t)ndx * ndx);
+    s.w_u.assign(ocp->w_u, ocp->w_u + (size_t)nu * nu);
+    s.w_cent.assign(ocp->w_cent, ocp->w_cent + 36);
+    s.w_frame.assign(ocp->w_frame, ocp->w_frame + fs * fs);
+    s.qmin.assign(ocp->qmin, ocp->qmin + na);
+    s.qmax.assign(ocp->qmax, ocp->qmax + na);
+    for (int i = 0; i < 3; i++)
+      s.gravity[i] = ocp->gravity[i];
+    s.mu = ocp->mu;
+    s.Lfoot = ocp->Lfoot;
+    s.Wfoot = ocp->Wfoot;
+    s.force_size = fs;
+    s.kinematics_limits = ocp->kinematics_limits;
+    s.force_cone = ocp->force_cone;
+    s.terminal_constraint = ocp->terminal_constraint;
+    return s;
+  }
+  unsigned contact_bits(const uint8_t * contact, int nf)
+  {
+    unsigned mask = 0;
+    for (int k = 0; k < nf; k++)
+      mask |= contact[k] ? (1u << k) : 0u;
+    return mask;
+  }
+  int get_output(smpc_handle * h, Output what, double * out)
+  {
+    if (!h || !out)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { h->e->get_output(what, out); });
+  }
   // one control step has been enqueued: with retention on, the state derivatives of every stage at its iterate (one launch on the stream)
   void retain_after_iterate(smpc_handle * h)
   {
     if (!h->retain_xdot)
       return;
-    if (h->full)
-      h->full->state_derivatives(h->xdot_all);
-    else if (h->cent)
-      h->cent->state_derivatives(h->xdot_all);
-    else
-      h->eng->state_derivatives(h->xdot_all);
+    h->e->state_derivatives(h->xdot_all);
     h->xdot_state = smpc_handle::XDOT_VALID;
   }
   // why the retained state derivatives cannot be read, or null
@@ -152,58 +195,33 @@ extern "C"
       return fail(SMPC_ERR_INVALID, "force size in settings does not match reference force size");
     if (mpc->T < 2)
       return fail(SMPC_ERR_INVALID, "horizon must have at least 2 stages");
+    const HostMpcSettings ms = host_mpc(mpc);
     if (ocp->force_size == 6)
     {
       // 6-D (flat) feet: the kinodynamics variant of the dense stage / solver kernels (FullDims<..., KIN = 1>, smpc_full_model.h)
       if (robot->njoints != KinoTalos::NJ || robot->nfeet != KinoTalos::NF)
         return fail(SMPC_ERR_INVALID, "robot shape (njoints, nfeet, force_size) does not match a built kernel instantiation");
       const int nv = robot->nv, ndx = 2 * nv, na = nv - 6, nu = na + 6 * robot->nfeet;
-      HostFullSettings s;
-      s.timestep = ocp->timestep;
-      s.w_x.assign(ocp->w_x, ocp->w_x + (size_t)ndx * ndx);
-      s.w_u.assign(ocp->w_u, ocp->w_u + (size_t)nu * nu);
-      s.w_cent.assign(ocp->w_cent, ocp->w_cent + 36);
+      HostFullSettings s = host_full(ocp, ndx, nu, na, 6);
       s.w_centder.assign(ocp->w_centder, ocp->w_centder + 36);
       s.w_forces.assign(36, 0.0);
-      s.w_frame.assign(ocp->w_frame, ocp->w_frame + 36);
       s.umin.assign(nu, 0.0); // (no torque box in this OCP)
       s.umax.assign(nu, 0.0);
-      s.qmin.assign(ocp->qmin, ocp->qmin + na);
-      s.qmax.assign(ocp->qmax, ocp->qmax + na);
       s.Kp.assign(6, 0.0);
       s.Kd.assign(6, 0.0);
-      for (int i = 0; i < 3; i++)
-        s.gravity[i] = ocp->gravity[i];
-      s.mu = ocp->mu;
-      s.Lfoot = ocp->Lfoot;
-      s.Wfoot = ocp->Wfoot;
-      s.force_size = 6;
       s.torque_limits = 0;
-      s.kinematics_limits = ocp->kinematics_limits;
-      s.force_cone = ocp->force_cone;
       s.land_cstr = 0; // (src/kinodynamics.cpp:134-146: land rows exist for 3-D feet only)
-      s.terminal_constraint = ocp->terminal_constraint;
       for (int i = 0; i < na; i++)
         if (!(s.qmin[i] <= s.qmax[i]))
           return fail(SMPC_ERR_INVALID, "qmin must not exceed qmax (joint limits are indexed by actuated joint, 0 .. nv - 7)");
-      auto sym = [](const std::vector<double> & w, int n) {
-        for (int i = 0; i < n; i++)
-          for (int j = 0; j < i; j++)
-            if (std::fabs(w[(size_t)i * n + j] - w[(size_t)j * n + i]) > 1e-12 * (1.0 + std::fabs(w[(size_t)i * n + j])))
-              return false;
-        return true;
-      };
-      if (!sym(s.w_x, ndx) || !sym(s.w_u, nu) || !sym(s.w_cent, 6) || !sym(s.w_centder, 6) || !sym(s.w_frame, 6))
+      if (!symmetric(s.w_x, ndx) || !symmetric(s.w_u, nu) || !symmetric(s.w_cent, 6) || !symmetric(s.w_centder, 6) || !symmetric(s.w_frame, 6))
         return fail(SMPC_ERR_INVALID, "weight matrices must be symmetric");
-      const HostMpcSettings ms6 = host_mpc(mpc);
-      return guarded([&] {
-        std::unique_ptr<smpc_handle> h(new smpc_handle());
+      return create_handle(out, [&]() -> MpcEngineBase * {
 #if !defined(SMPC_KINO_ONLY) || defined(SMPC_TALOS_TOO) // (experiment builds: -DSMPC_KINO_ONLY -DSMPC_TALOS_TOO = Go2 kinodynamics + the biped's two dense engines)
-        h->full.reset(new FullEngine<KinoTalos>(robot, s, ms6, batch, gravity_arg, device_id));
+        return new FullEngine<KinoTalos>(robot, s, ms, batch, gravity_arg, device_id);
 #else
         throw std::runtime_error("SMPC_KINO_ONLY experiment build");
 #endif
-        *out = h.release();
       });
     }
     const int nv = robot->nv, ndx = 2 * nv, nu = nv - 6 + 3 * robot->nfeet;
@@ -226,34 +244,16 @@ extern "C"
     for (int i = 0; i < nv - 6; i++)
       if (!(ks.qmin[i] <= ks.qmax[i]))
         return fail(SMPC_ERR_INVALID, "qmin must not exceed qmax (joint limits are indexed by actuated joint, 0 .. nv - 7)");
-    // the weights enter the Gauss-Newton Hessian as they are: they must be symmetric
-    for (int i = 0; i < ndx; i++)
-      for (int j = 0; j < i; j++)
-        if (std::fabs(ks.w_x[(size_t)i * ndx + j] - ks.w_x[(size_t)j * ndx + i]) > 1e-12 * (1.0 + std::fabs(ks.w_x[(size_t)i * ndx + j])))
-          return fail(SMPC_ERR_INVALID, "w_x must be symmetric");
-    for (int i = 0; i < nu; i++)
-      for (int j = 0; j < i; j++)
-        if (std::fabs(ks.w_u[(size_t)i * nu + j] - ks.w_u[(size_t)j * nu + i]) > 1e-12 * (1.0 + std::fabs(ks.w_u[(size_t)i * nu + j])))
-          return fail(SMPC_ERR_INVALID, "w_u must be symmetric");
-    HostMpcSettings ms;
-    ms.swing_apex = mpc->swing_apex;
-    ms.support_force = mpc->support_force;
-    ms.TOL = mpc->TOL;
-    ms.mu_init = mpc->mu_init;
-    ms.timestep = mpc->timestep;
-    ms.max_iters = mpc->max_iters;
-    ms.num_threads = mpc->num_threads;
-    ms.T_fly = mpc->T_fly;
-    ms.T_contact = mpc->T_contact;
-    ms.T = mpc->T;
-    return guarded([&] {
-      std::unique_ptr<smpc_handle> h(new smpc_handle());
+    if (!symmetric(ks.w_x, ndx))
+      return fail(SMPC_ERR_INVALID, "w_x must be symmetric");
+    if (!symmetric(ks.w_u, nu))
+      return fail(SMPC_ERR_INVALID, "w_u must be symmetric");
+    return create_handle(out, [&]() -> MpcEngineBase * {
 #ifdef SMPC_CENT_ONLY
       throw std::runtime_error("SMPC_CENT_ONLY experiment build");
 #else
-      h->eng.reset(new KinoEngine<DimsGo2>(robot, ks, ms, batch, gravity_arg, device_id));
+      return new KinoEngine<DimsGo2>(robot, ks, ms, batch, gravity_arg, device_id);
 #endif
-      *out = h.release();
     });
   }
   int smpc_create_centroidal(
@@ -287,33 +287,23 @@ extern "C"
     cs.Lfoot = ocp->Lfoot;
     cs.Wfoot = ocp->Wfoot;
     cs.force_size = ocp->force_size;
-    auto sym = [](const std::vector<double> & w, int n) {
-      for (int i = 0; i < n; i++)
-        for (int j = 0; j < i; j++)
-          if (std::fabs(w[(size_t)i * n + j] - w[(size_t)j * n + i]) > 1e-12 * (1.0 + std::fabs(w[(size_t)i * n + j])))
-            return false;
-      return true;
-    };
-    if (!sym(cs.w_u, nu) || !sym(cs.w_com, 3) || !sym(cs.w_linear_mom, 3) || !sym(cs.w_angular_mom, 3) || !sym(cs.w_linear_acc, 3)
-        || !sym(cs.w_angular_acc, 3))
+    if (!symmetric(cs.w_u, nu) || !symmetric(cs.w_com, 3) || !symmetric(cs.w_linear_mom, 3) || !symmetric(cs.w_angular_mom, 3)
+        || !symmetric(cs.w_linear_acc, 3) || !symmetric(cs.w_angular_acc, 3))
       return fail(SMPC_ERR_INVALID, "weight matrices must be symmetric");
     const HostMpcSettings ms = host_mpc(mpc);
-    return guarded([&] {
-      std::unique_ptr<smpc_handle> h(new smpc_handle());
+    return create_handle(out, [&]() -> MpcEngineBase * {
 #if !defined(SMPC_KINO_ONLY) || defined(SMPC_XCHECK_SUBSET) // (the cross-check HIP build: Go2 kinodynamics + both centroidal engines)
       if (quad)
-        h->cent.reset(new CentEngine<FullTalos, CentTalos>(robot, cs, ms, batch, gravity_arg, device_id));
-      else
-        h->cent.reset(new CentEngineGo2(robot, cs, ms, batch, gravity_arg, device_id));
+        return new CentEngine<FullTalos, CentTalos>(robot, cs, ms, batch, gravity_arg, device_id);
+      return new CentEngineGo2(robot, cs, ms, batch, gravity_arg, device_id);
 #elif defined(SMPC_CENT_ONLY)
       if (quad)
         throw std::runtime_error("SMPC_CENT_ONLY experiment build");
-      h->cent.reset(new CentEngineGo2(robot, cs, ms, batch, gravity_arg, device_id));
+      return new CentEngineGo2(robot, cs, ms, batch, gravity_arg, device_id);
 #else
       (void)quad;
       throw std::runtime_error("SMPC_KINO_ONLY experiment build");
 #endif
-      *out = h.release();
     });
   }
   int smpc_create_fulldynamics(
@@ -330,83 +320,47 @@ extern "C"
     if (mpc->T < 2)
       return fail(SMPC_ERR_INVALID, "horizon must have at least 2 stages");
     const int nv = robot->nv, ndx = 2 * nv, nu = nv - 6, fs = ocp->force_size;
-    HostFullSettings s;
-    s.timestep = ocp->timestep;
-    s.w_x.assign(ocp->w_x, ocp->w_x + (size_t)ndx * ndx);
-    s.w_u.assign(ocp->w_u, ocp->w_u + (size_t)nu * nu);
-    s.w_cent.assign(ocp->w_cent, ocp->w_cent + 36);
+    HostFullSettings s = host_full(ocp, ndx, nu, nu, fs);
     s.w_forces.assign(ocp->w_forces, ocp->w_forces + fs * fs);
-    s.w_frame.assign(ocp->w_frame, ocp->w_frame + fs * fs);
     s.umin.assign(ocp->umin, ocp->umin + nu);
     s.umax.assign(ocp->umax, ocp->umax + nu);
-    s.qmin.assign(ocp->qmin, ocp->qmin + nu);
-    s.qmax.assign(ocp->qmax, ocp->qmax + nu);
     s.Kp.assign(ocp->Kp_correction, ocp->Kp_correction + fs);
     s.Kd.assign(ocp->Kd_correction, ocp->Kd_correction + fs);
-    for (int i = 0; i < 3; i++)
-      s.gravity[i] = ocp->gravity[i];
-    s.mu = ocp->mu;
-    s.Lfoot = ocp->Lfoot;
-    s.Wfoot = ocp->Wfoot;
-    s.force_size = fs;
     s.torque_limits = ocp->torque_limits;
-    s.kinematics_limits = ocp->kinematics_limits;
-    s.force_cone = ocp->force_cone;
     s.land_cstr = ocp->land_cstr;
-    s.terminal_constraint = ocp->terminal_constraint;
     for (int i = 0; i < nu; i++)
       if (!(s.qmin[i] <= s.qmax[i]) || !(s.umin[i] <= s.umax[i]))
         return fail(SMPC_ERR_INVALID, "lower limits must not exceed upper limits (indexed by actuated joint, 0 .. nv - 7)");
-    auto sym = [](const std::vector<double> & w, int n) {
-      for (int i = 0; i < n; i++)
-        for (int j = 0; j < i; j++)
-          if (std::fabs(w[(size_t)i * n + j] - w[(size_t)j * n + i]) > 1e-12 * (1.0 + std::fabs(w[(size_t)i * n + j])))
-            return false;
-      return true;
-    };
-    if (!sym(s.w_x, ndx) || !sym(s.w_u, nu) || !sym(s.w_cent, 6) || !sym(s.w_forces, fs) || !sym(s.w_frame, fs))
+    if (!symmetric(s.w_x, ndx) || !symmetric(s.w_u, nu) || !symmetric(s.w_cent, 6) || !symmetric(s.w_forces, fs) || !symmetric(s.w_frame, fs))
       return fail(SMPC_ERR_INVALID, "weight matrices must be symmetric");
     const HostMpcSettings ms = host_mpc(mpc);
-    return guarded([&] {
-      std::unique_ptr<smpc_handle> h(new smpc_handle());
+    return create_handle(out, [&]() -> MpcEngineBase * {
 #if defined(SMPC_KINO_ONLY) && defined(SMPC_TALOS_TOO)
       if (robot->njoints == FullTalos::NJ && robot->nfeet == FullTalos::NF && fs == FullTalos::FS && !s.land_cstr)
-        h->full.reset(new FullEngine<FullTalos>(robot, s, ms, batch, gravity_arg, device_id));
-      else
-        throw std::runtime_error("SMPC_KINO_ONLY experiment build");
+        return new FullEngine<FullTalos>(robot, s, ms, batch, gravity_arg, device_id);
+      throw std::runtime_error("SMPC_KINO_ONLY experiment build");
 #elif defined(SMPC_KINO_ONLY) && defined(SMPC_GO2FULL_TOO)
       if (robot->njoints == FullGo2::NJ && robot->nfeet == FullGo2::NF && fs == FullGo2::FS && !s.land_cstr && !s.force_cone)
-        h->full.reset(new FullEngine<FullGo2>(robot, s, ms, batch, gravity_arg, device_id));
-      else
-        throw std::runtime_error("SMPC_KINO_ONLY experiment build");
+        return new FullEngine<FullGo2>(robot, s, ms, batch, gravity_arg, device_id);
+      throw std::runtime_error("SMPC_KINO_ONLY experiment build");
 #elif defined(SMPC_KINO_ONLY)
       throw std::runtime_error("SMPC_KINO_ONLY experiment build");
 #else
       if (robot->njoints == FullGo2::NJ && robot->nfeet == FullGo2::NF && fs == FullGo2::FS && s.land_cstr && s.force_cone)
-        h->full.reset(new FullEngine<FullGo2ConeLand>(robot, s, ms, batch, gravity_arg, device_id));
-      else if (robot->njoints == FullGo2::NJ && robot->nfeet == FullGo2::NF && fs == FullGo2::FS && s.land_cstr)
-        h->full.reset(new FullEngine<FullGo2Land>(robot, s, ms, batch, gravity_arg, device_id));
-      else if (robot->njoints == FullTalos::NJ && robot->nfeet == FullTalos::NF && fs == FullTalos::FS && s.land_cstr)
-        h->full.reset(new FullEngine<FullTalosLand>(robot, s, ms, batch, gravity_arg, device_id));
-      else if (robot->njoints == FullGo2::NJ && robot->nfeet == FullGo2::NF && fs == FullGo2::FS && s.force_cone)
-        h->full.reset(new FullEngine<FullGo2Cone>(robot, s, ms, batch, gravity_arg, device_id));
-      else if (robot->njoints == FullGo2::NJ && robot->nfeet == FullGo2::NF && fs == FullGo2::FS)
-        h->full.reset(new FullEngine<FullGo2>(robot, s, ms, batch, gravity_arg, device_id));
-      else if (robot->njoints == FullTalos::NJ && robot->nfeet == FullTalos::NF && fs == FullTalos::FS)
-        h->full.reset(new FullEngine<FullTalos>(robot, s, ms, batch, gravity_arg, device_id));
-      else
-        throw std::runtime_error("robot shape (njoints, nfeet, force_size) does not match a built kernel instantiation");
+        return new FullEngine<FullGo2ConeLand>(robot, s, ms, batch, gravity_arg, device_id);
+      if (robot->njoints == FullGo2::NJ && robot->nfeet == FullGo2::NF && fs == FullGo2::FS && s.land_cstr)
+        return new FullEngine<FullGo2Land>(robot, s, ms, batch, gravity_arg, device_id);
+      if (robot->njoints == FullTalos::NJ && robot->nfeet == FullTalos::NF && fs == FullTalos::FS && s.land_cstr)
+        return new FullEngine<FullTalosLand>(robot, s, ms, batch, gravity_arg, device_id);
+      if (robot->njoints == FullGo2::NJ && robot->nfeet == FullGo2::NF && fs == FullGo2::FS && s.force_cone)
+        return new FullEngine<FullGo2Cone>(robot, s, ms, batch, gravity_arg, device_id);
+      if (robot->njoints == FullGo2::NJ && robot->nfeet == FullGo2::NF && fs == FullGo2::FS)
+        return new FullEngine<FullGo2>(robot, s, ms, batch, gravity_arg, device_id);
+      if (robot->njoints == FullTalos::NJ && robot->nfeet == FullTalos::NF && fs == FullTalos::FS)
+        return new FullEngine<FullTalos>(robot, s, ms, batch, gravity_arg, device_id);
+      throw std::runtime_error("robot shape (njoints, nfeet, force_size) does not match a built kernel instantiation");
 #endif
-      *out = h.release();
     });
-  }
-  int smpc_get_contact_forces(smpc_handle * h, double * out)
-  {
-    if (!h || !out)
-      return fail(SMPC_ERR_INVALID, "null argument");
-    if (!h->full)
-      return fail(SMPC_ERR_INVALID, "smpc_get_contact_forces needs a full-dynamics handle (the other problems carry the forces in us)");
-    return guarded([&] { h->full->get(9, out); });
   }
   int smpc_destroy(smpc_handle * h)
   {
@@ -417,113 +371,56 @@ extern "C"
   {
     if (!h || !d)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-    {
-      for (int i = 0; i < 8; i++)
-        d[i] = h->full->dims[i];
-      return SMPC_OK;
-    }
-    if (h->cent)
-    {
-      d[0] = h->cent->nq_mb;
-      d[1] = h->cent->nv_mb;
-      d[2] = 9;
-      d[3] = 9;
-      d[4] = h->cent->nu;
-      d[5] = h->cent->nc;
-      d[6] = h->cent->nf;
-      d[7] = h->cent->H;
-      return SMPC_OK;
-    }
-    d[0] = DimsGo2::NQ;
-    d[1] = DimsGo2::NV;
-    d[2] = DimsGo2::NX;
-    d[3] = DimsGo2::NDX;
-    d[4] = DimsGo2::NU;
-    d[5] = DimsGo2::NC;
-    d[6] = DimsGo2::NF;
-    d[7] = h->eng->H;
+    std::copy(h->e->dims, h->e->dims + 8, d);
     return SMPC_OK;
   }
   int smpc_generate_cycle_horizon(smpc_handle * h, const uint8_t * cs, int n)
   {
     if (!h || !cs)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->generate_cycle_horizon(cs, n); });
-    if (h->cent)
-      return guarded([&] { h->cent->generate_cycle_horizon(cs, n); });
-    return guarded([&] { h->eng->generate_cycle_horizon(cs, n); });
+    return guarded([&] { h->e->generate_cycle_horizon(cs, n); });
   }
   int smpc_switch_to_walk(smpc_handle * h, const double * v6)
   {
     if (!h || !v6)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->switch_to_walk(v6); });
-    if (h->cent)
-      return guarded([&] { h->cent->switch_to_walk(v6); });
-    return guarded([&] { h->eng->switch_to_walk(v6); });
+    return guarded([&] { h->e->switch_to_walk(v6); });
   }
   int smpc_switch_to_stand(smpc_handle * h)
   {
     if (!h)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->switch_to_stand(); });
-    if (h->cent)
-      return guarded([&] { h->cent->switch_to_stand(); });
-    return guarded([&] { h->eng->switch_to_stand(); });
+    return guarded([&] { h->e->switch_to_stand(); });
   }
   int smpc_set_velocity_base_batched(smpc_handle * h, const double * V)
   {
     if (!h || !V)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->set_velocity_base_batched(V); });
-    if (h->cent)
-      return guarded([&] { h->cent->set_velocity_base_batched(V); });
-    return guarded([&] { h->eng->set_velocity_base_batched(V); });
+    return guarded([&] { h->e->set_velocity_base_batched(V); });
   }
   int smpc_set_stage_reference(smpc_handle * h, int t, int what, const double * v, int n)
   {
     if (!h || !v)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->set_stage_reference(t, what, v, n); });
-    if (h->cent)
-      return guarded([&] { h->cent->set_stage_reference(t, what, v, n); });
-    return guarded([&] { h->eng->set_stage_reference(t, what, v, n); });
+    return guarded([&] { h->e->set_stage_reference(t, what, v, n); });
   }
   int smpc_get_stage_reference(smpc_handle * h, int t, int what, double * v, int n)
   {
     if (!h || !v)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->get_stage_reference(t, what, v, n); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_stage_reference(t, what, v, n); });
-    return guarded([&] { h->eng->get_stage_reference(t, what, v, n); });
+    return guarded([&] { h->e->get_stage_reference(t, what, v, n); });
   }
   int smpc_set_reference_pose(smpc_handle * h, int t, int foot, const double * p3)
   {
     if (!h || !p3)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->set_reference_pose(t, foot, p3); });
-    if (h->cent)
-      return guarded([&] { h->cent->set_reference_pose(t, foot, p3); });
-    return guarded([&] { h->eng->set_reference_pose(t, foot, p3); });
+    return guarded([&] { h->e->set_reference_pose(t, foot, p3); });
   }
   int smpc_get_reference_pose(smpc_handle * h, int t, int foot, int instance, double * p3)
   {
     if (!h || !p3)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->get_reference_pose(t, foot, instance, p3); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_reference_pose(t, foot, instance, p3); });
-    return guarded([&] { h->eng->get_reference_pose(t, foot, instance, p3); });
+    return guarded([&] { h->e->get_reference_pose(t, foot, instance, p3); });
   }
   int smpc_set_reference_pose_se3(smpc_handle * h, int t, int foot, const double * p3, const double * R9)
   {
@@ -532,11 +429,7 @@ extern "C"
     const int rc = smpc_set_reference_pose(h, t, foot, p3);
     if (rc != SMPC_OK)
       return rc;
-    if (h->full)
-      return guarded([&] { h->full->set_reference_rotation(t, foot, R9); });
-    if (h->cent)
-      return guarded([&] { h->cent->set_reference_rotation(t, foot, R9); });
-    return guarded([&] { h->eng->set_reference_rotation(t, foot, R9); });
+    return guarded([&] { h->e->set_reference_rotation(t, foot, R9); });
   }
   int smpc_get_reference_pose_se3(smpc_handle * h, int t, int foot, int instance, double * p3, double * R9)
   {
@@ -545,20 +438,15 @@ extern "C"
     const int rc = smpc_get_reference_pose(h, t, foot, instance, p3);
     if (rc != SMPC_OK)
       return rc;
-    if (h->full)
-      return guarded([&] { h->full->get_reference_rotation(t, foot, R9); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_reference_rotation(t, foot, R9); });
-    return guarded([&] { h->eng->get_reference_rotation(t, foot, R9); });
+    return guarded([&] { h->e->get_reference_rotation(t, foot, R9); });
   }
   int smpc_get_contact_state(smpc_handle * h, int t, uint8_t * out)
   {
     if (!h || !out)
       return fail(SMPC_ERR_INVALID, "null argument");
     return guarded([&] {
-      const unsigned m = h->full ? h->full->contact_mask(t) : (h->cent ? h->cent->contact_mask(t) : h->eng->contact_mask(t));
-      const int nf = h->full ? h->full->dims[6] : (h->cent ? h->cent->nf : DimsGo2::NF);
-      for (int f = 0; f < nf; f++)
+      const unsigned m = h->e->contact_mask(t);
+      for (int f = 0; f < h->e->dims[6]; f++)
         out[f] = (m >> f) & 1u;
     });
   }
@@ -566,7 +454,7 @@ extern "C"
   {
     if (!h)
       return fail(SMPC_ERR_INVALID, "null argument");
-    const GaitTimer & tm = h->full ? h->full->timer : (h->cent ? h->cent->timer : h->eng->timer);
+    const GaitTimer & tm = h->e->timer;
     const int n = (int)tm.states.size();
     if (!out)
       return n;
@@ -582,12 +470,7 @@ extern "C"
   {
     if (!h || !x)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      h->full->x_reference.assign(x, x + h->full->dims[2]);
-    else if (h->cent)
-      std::copy(x, x + 9, h->cent->x_reference);
-    else
-      h->eng->x_reference.assign(x, x + DimsGo2::NX);
+    h->e->x_reference.assign(x, x + h->e->dims[2]);
     return SMPC_OK;
   }
   int smpc_iterate(smpc_handle * h, const double * X)
@@ -595,30 +478,12 @@ extern "C"
     if (!h || !X)
       return fail(SMPC_ERR_INVALID, "null argument");
     h->xdot_state = smpc_handle::XDOT_NONE;
-    if (h->full)
-      return guarded([&] {
-        h->full->iterate_host(X);
-        if (h->retain_xdot)
-        {
-          retain_after_iterate(h);
-          h->full->sync();
-        }
-      });
-    if (h->cent)
-      return guarded([&] {
-        h->cent->iterate_host(X);
-        if (h->retain_xdot)
-        {
-          retain_after_iterate(h);
-          h->cent->sync();
-        }
-      });
     return guarded([&] {
-      h->eng->iterate_host(X);
+      h->e->iterate_host(X);
       if (h->retain_xdot)
       {
         retain_after_iterate(h);
-        h->eng->sync();
+        h->e->sync();
       }
     });
   }
@@ -627,18 +492,8 @@ extern "C"
     if (!h || !X)
       return fail(SMPC_ERR_INVALID, "null argument");
     h->xdot_state = smpc_handle::XDOT_NONE;
-    if (h->full)
-      return guarded([&] {
-        h->full->iterate_host(X); // (synchronous on these handles)
-        retain_after_iterate(h);
-      });
-    if (h->cent)
-      return guarded([&] {
-        h->cent->iterate_host(X);
-        retain_after_iterate(h);
-      });
     return guarded([&] {
-      h->eng->iterate_host_async(X);
+      h->e->iterate_host_async(X); // (synchronous on full-dynamics and centroidal handles)
       retain_after_iterate(h);
     });
   }
@@ -646,45 +501,27 @@ extern "C"
   {
     if (!h || !out)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (!h->eng)
-      return fail(SMPC_ERR_INVALID, KINO_ONLY);
-    return guarded([&] { h->eng->gather_outputs_async(out, row_doubles); });
+    return guarded([&] { h->e->gather_outputs_async(out, row_doubles); });
   }
   int smpc_gather_outputs_device(smpc_handle * h, double * out_device, size_t row_doubles)
   {
     if (!h || !out_device)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (!h->eng)
-      return fail(SMPC_ERR_INVALID, KINO_ONLY);
-    return guarded([&] { h->eng->gather_outputs_device(out_device, row_doubles); });
+    return guarded([&] { h->e->gather_outputs_device(out_device, row_doubles); });
   }
   int smpc_gather_outputs_peer(smpc_handle * h, double * out_peer, int dst_device)
   {
     if (!h || !out_peer)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (!h->eng)
-      return fail(SMPC_ERR_INVALID, KINO_ONLY);
-    if (dst_device < 0 || dst_device >= device_count())
-      return fail(SMPC_ERR_INVALID, "destination device out of range");
-    return guarded([&] { h->eng->gather_outputs_peer(out_peer, dst_device); });
+    return guarded([&] { h->e->gather_outputs_peer(out_peer, dst_device); });
   }
   int smpc_iterate_device(smpc_handle * h, const double * Xd)
   {
     if (!h || !Xd)
       return fail(SMPC_ERR_INVALID, "null argument");
     h->xdot_state = smpc_handle::XDOT_NONE;
-    if (h->full)
-      return guarded([&] {
-        h->full->iterate_device(Xd);
-        retain_after_iterate(h);
-      });
-    if (h->cent)
-      return guarded([&] {
-        h->cent->iterate_device(Xd);
-        retain_after_iterate(h);
-      });
     return guarded([&] {
-      h->eng->iterate_device(Xd);
+      h->e->iterate_device(Xd);
       retain_after_iterate(h);
     });
   }
@@ -692,32 +529,13 @@ extern "C"
   {
     if (!h)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->sync(); });
-    if (h->cent)
-      return guarded([&] { h->cent->sync(); });
-    return guarded([&] { h->eng->sync(); });
+    return guarded([&] { h->e->sync(); });
   }
-  void * smpc_get_stream(smpc_handle * h)
-  {
-    if (!h)
-      return nullptr;
-    return stream_native(h->full ? h->full->stream : (h->cent ? h->cent->stream : h->eng->stream));
-  }
+  void * smpc_get_stream(smpc_handle * h) { return h ? stream_native(h->e->stream) : nullptr; }
   static size_t state_pass(smpc_handle * h, StateIO::Mode mode, void * buf, size_t cap)
   {
-    if (h->full)
-    {
-      StateIO io(mode, buf, cap, h->full->stream);
-      return h->full->state_io(io);
-    }
-    if (h->cent)
-    {
-      StateIO io(mode, buf, cap, h->cent->stream);
-      return h->cent->state_io(io);
-    }
-    StateIO io(mode, buf, cap, h->eng->stream);
-    return h->eng->state_io(io);
+    StateIO io(mode, buf, cap, h->e->stream);
+    return h->e->state_io(io);
   }
   int smpc_state_size(smpc_handle * h, size_t * bytes)
   {
@@ -747,97 +565,23 @@ extern "C"
   {
     if (!h || !out_device)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->gather_x_device(t, out_device); });
-    if (h->cent)
-      return fail(SMPC_ERR_INVALID, KINO_ONLY);
-    return guarded([&] { h->eng->gather_x_device(t, out_device); });
+    return guarded([&] { h->e->gather_x_device(t, out_device); });
   }
-  int smpc_get_xs(smpc_handle * h, double * out)
-  {
-    if (h->full)
-      return guarded([&] { h->full->get(0, out); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_ring(h->cent->bufs().xs, 9, h->cent->H + 1, out); });
-    return guarded([&] { h->eng->get_ring(h->eng->buf.xs, DimsGo2::NX, h->eng->H + 1, out); });
-  }
-  int smpc_get_us(smpc_handle * h, double * out)
-  {
-    if (h->full)
-      return guarded([&] { h->full->get(1, out); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_ring(h->cent->bufs().us, h->cent->nu, h->cent->H, out); });
-    return guarded([&] { h->eng->get_ring(h->eng->buf.us, DimsGo2::NU, h->eng->H, out); });
-  }
-  int smpc_get_vs(smpc_handle * h, double * out)
-  {
-    if (h->full)
-      return guarded([&] { h->full->get(4, out); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_ring(h->cent->bufs().vs, h->cent->nc, h->cent->H, out); });
-    return guarded([&] { h->eng->get_ring(h->eng->buf.vs, DimsGo2::NC, h->eng->H, out); });
-  }
+  int smpc_get_xs(smpc_handle * h, double * out) { return get_output(h, OUT_XS, out); }
+  int smpc_get_us(smpc_handle * h, double * out) { return get_output(h, OUT_US, out); }
+  int smpc_get_vs(smpc_handle * h, double * out) { return get_output(h, OUT_VS, out); }
+  int smpc_get_lams(smpc_handle * h, double * out) { return get_output(h, OUT_LAMS, out); }
+  int smpc_get_K0(smpc_handle * h, double * out) { return get_output(h, OUT_K0, out); }
+  int smpc_get_Ks(smpc_handle * h, double * out) { return get_output(h, OUT_KS, out); }
+  int smpc_get_state_derivative01(smpc_handle * h, double * out) { return get_output(h, OUT_XDOT01, out); }
+  int smpc_get_reference_poses(smpc_handle * h, double * out) { return get_output(h, OUT_FOOT_REFS, out); }
+  int smpc_get_info(smpc_handle * h, double * out) { return get_output(h, OUT_INFO, out); }
+  int smpc_get_contact_forces(smpc_handle * h, double * out) { return get_output(h, OUT_CONTACT_FORCES, out); }
   int smpc_debug_get_extra_multipliers(smpc_handle * h, int which, double * out)
   {
-    if (!h || !out || h->full || h->cent)
-      return fail(SMPC_ERR_INVALID, "kinodynamics handles only");
-    double * src = which == 0 ? h->eng->buf.es : h->eng->buf.ls;
-    if (!src)
-      return fail(SMPC_ERR_INVALID, "the problem has no such rows");
-    return guarded([&] { h->eng->get_ring(src, which == 0 ? 2 * DimsGo2::NF : DimsGo2::NF, h->eng->H, out); });
-  }
-  int smpc_get_lams(smpc_handle * h, double * out)
-  {
-    if (h->full)
-      return guarded([&] { h->full->get(5, out); });
-    // device arrays hold lambda_{t+1} at stage t; the API returns lams[0..H] with lams[0] = 0
-    if (h->cent)
-      return guarded([&] {
-        auto & e = *h->cent;
-        std::vector<double> tmp((size_t)e.B * e.H * 9);
-        e.get_ring(e.bufs().lams, 9, e.H, tmp.data());
-        for (int b = 0; b < e.B; b++)
-        {
-          double * o = out + (size_t)b * (e.H + 1) * 9;
-          std::memset(o, 0, 9 * sizeof(double));
-          std::memcpy(o + 9, tmp.data() + (size_t)b * e.H * 9, (size_t)e.H * 9 * sizeof(double));
-        }
-      });
-    return guarded([&] {
-      auto & e = *h->eng;
-      std::vector<double> tmp((size_t)e.B * e.H * DimsGo2::NDX);
-      e.get_ring(e.buf.lams, DimsGo2::NDX, e.H, tmp.data());
-      for (int b = 0; b < e.B; b++)
-      {
-        double * o = out + (size_t)b * (e.H + 1) * DimsGo2::NDX;
-        std::memset(o, 0, DimsGo2::NDX * sizeof(double));
-        std::memcpy(o + DimsGo2::NDX, tmp.data() + (size_t)b * e.H * DimsGo2::NDX, (size_t)e.H * DimsGo2::NDX * sizeof(double));
-      }
-    });
-  }
-  int smpc_get_K0(smpc_handle * h, double * out)
-  {
-    if (h->full)
-      return guarded([&] { h->full->get(2, out); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_K(out, false); });
-    return guarded([&] { h->eng->get_K(out, false); });
-  }
-  int smpc_get_Ks(smpc_handle * h, double * out)
-  {
-    if (h->full)
-      return guarded([&] { h->full->get(3, out); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_K(out, true); });
-    return guarded([&] { h->eng->get_K(out, true); });
-  }
-  int smpc_get_state_derivative01(smpc_handle * h, double * out)
-  {
-    if (h->full)
-      return guarded([&] { h->full->get(6, out); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_linear(h->cent->bufs().xdot01, (size_t)h->cent->B * 18, out); });
-    return guarded([&] { h->eng->get_linear(h->eng->buf.xdot01, (size_t)h->eng->B * 4 * DimsGo2::NV, out); });
+    if (!h || !out)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { h->e->get_extra_multipliers(which, out); });
   }
   int smpc_set_retain_state_derivatives(smpc_handle * h, int on)
   {
@@ -855,8 +599,8 @@ extern "C"
     {
       try
       {
-        set_device(h->device());
-        h->xdot_all = (double *)dev_alloc(h->xdot_doubles() * sizeof(double));
+        set_device(h->e->device_id);
+        h->xdot_all = (double *)dev_alloc(h->e->xdot_doubles() * sizeof(double));
       }
       catch (const std::exception & e)
       {
@@ -875,10 +619,11 @@ extern "C"
     if (const char * why = xdot_refusal(h))
       return fail(SMPC_ERR_INVALID, why);
     return guarded([&] {
-      set_device(h->device());
-      stream_sync(h->stream());
-      d2h(out, h->xdot_all, h->xdot_doubles() * sizeof(double), h->stream());
-      stream_sync(h->stream());
+      const stream_t st = h->e->stream;
+      set_device(h->e->device_id);
+      stream_sync(st);
+      d2h(out, h->xdot_all, h->e->xdot_doubles() * sizeof(double), st);
+      stream_sync(st);
     });
   }
   int smpc_get_state_derivatives_device(smpc_handle * h, double * out_device)
@@ -888,21 +633,13 @@ extern "C"
     if (const char * why = xdot_refusal(h))
       return fail(SMPC_ERR_INVALID, why);
     return guarded([&] {
-      set_device(h->device());
-      d2d(out_device, h->xdot_all, h->xdot_doubles() * sizeof(double), h->stream());
+      set_device(h->e->device_id);
+      d2d(out_device, h->xdot_all, h->e->xdot_doubles() * sizeof(double), h->e->stream);
     });
-  }
-  int smpc_get_reference_poses(smpc_handle * h, double * out)
-  {
-    if (h->full)
-      return guarded([&] { h->full->get(7, out); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_linear(h->cent->bufs().foot, (size_t)h->cent->B * h->cent->H * h->cent->nf * 3, out); });
-    return guarded([&] { h->eng->get_linear(h->eng->buf.foot_ref, (size_t)h->eng->B * h->eng->H * DimsGo2::NF * 3, out); });
   }
   int smpc_get_foot_timing(smpc_handle * h, int foot, int which, int * out, int cap)
   {
-    const GaitTimer * tm = !h ? nullptr : (h->full ? &h->full->timer : (h->cent ? &h->cent->timer : &h->eng->timer));
+    const GaitTimer * tm = h ? &h->e->timer : nullptr;
     if (!tm || foot < 0 || foot >= tm->nf || tm->nf == 0)
     {
       fail(SMPC_ERR_INVALID, "invalid foot index or cycle horizon not generated");
@@ -913,19 +650,11 @@ extern "C"
       out[i] = v[i];
     return (int)v.size();
   }
-  int smpc_get_info(smpc_handle * h, double * out)
-  {
-    if (h->full)
-      return guarded([&] { h->full->get(8, out); });
-    if (h->cent)
-      return guarded([&] { h->cent->get_linear(h->cent->bufs().scal, (size_t)h->cent->B * SC_N, out); });
-    return guarded([&] { h->eng->get_linear(h->eng->buf.scal, (size_t)h->eng->B * SC_N, out); });
-  }
   int smpc_get_status(smpc_handle * h, int * out)
   {
     if (!h || !out)
       return fail(SMPC_ERR_INVALID, "null argument");
-    const int B = h->full ? h->full->B : (h->cent ? h->cent->B : h->eng->B);
+    const int B = h->e->B;
     std::vector<double> info((size_t)B * SC_N);
     const int rc = smpc_get_info(h, info.data());
     if (rc < 0)
@@ -949,145 +678,71 @@ extern "C"
   }
   int smpc_get_cold_trace(smpc_handle * h, double * out, int cap)
   {
-    const int n = h->full ? h->full->cold_iters : (h->cent ? h->cent->cold_iters : h->eng->cold_iters);
-    const std::vector<double> & tr = h->full ? h->full->cold_trace : (h->cent ? h->cent->cold_trace : h->eng->cold_trace);
+    if (!h || (!out && cap > 0))
+      return fail(SMPC_ERR_INVALID, "null argument");
+    const int n = h->e->cold_iters;
     for (int i = 0; i < n && i < cap; i++)
       for (int k = 0; k < 4; k++)
-        out[i * 4 + k] = tr[(size_t)i * 4 + k];
+        out[i * 4 + k] = h->e->cold_trace[(size_t)i * 4 + k];
     return n;
   }
-  // (size of what smpc_debug_get_lq returns: the row-major form of a kinodynamics knot)
+  // (size of what smpc_debug_get_lq returns.  A handle without knots of its own -- centroidal, null -- reports the row-major form of a
+  // Go2 kinodynamics knot, as this entry point always has.)
   int smpc_lq_size(const smpc_handle * h)
   {
-    typedef DimsGo2 D;
-    return (h && h->full) ? h->full->lq_size() : (D::O_T - D::O_A) + D::NDX * D::NDX + D::NDX * D::NU + D::NU * D::NU + (D::O_vpd + D::NC - D::O_C);
+    const int n = h ? h->e->lq_size() : 0;
+    return n ? n : kino_lq_size<DimsGo2>();
   }
   int smpc_set_early_exit_on_tol(smpc_handle * h, int on)
   {
     if (!h)
       return fail(SMPC_ERR_INVALID, "null handle");
-    if (h->cent)
-      return fail(SMPC_ERR_INVALID, "smpc_set_early_exit_on_tol: kinodynamics and full-dynamics handles (the centroidal step is one fused kernel)");
-    if (h->full)
-      return guarded([&] { h->full->set_early_exit(on != 0); });
-    h->eng->early_exit_on_tol = on != 0;
-    return SMPC_OK;
+    return guarded([&] { h->e->set_early_exit(on != 0); });
   }
   int smpc_debug_get_lq(smpc_handle * h, int inst, int t, double * out)
   {
-    if (h && h->full)
-      return guarded([&] { h->full->debug_lq(inst, t, out); });
-    if (h && h->cent)
-      return fail(SMPC_ERR_INVALID, KINO_ONLY);
-    if (!h || inst < 0 || inst >= h->eng->B || t < 0 || t >= h->eng->H)
-      return fail(SMPC_ERR_INVALID, "Stage index exceeds stage vector size");
-    return guarded([&] {
-      // the device keeps [Q S; S^T R] as accumulator-layout tiles (Dims::O_T); returned in the documented row-major order
-      // A | B | Q | S | R | C | q | r | f | d | lx | lu | lpd | vpd
-      typedef DimsGo2 D;
-      std::vector<double> raw(D::LQ_STRIDE);
-      h->eng->get_linear(h->eng->buf.lq + ((size_t)inst * h->eng->H + t) * D::LQ_STRIDE, D::LQ_STRIDE, raw.data());
-      constexpr int n = D::NDX, m = D::NU;
-      double * o = out;
-      std::copy(raw.begin() + D::O_A, raw.begin() + D::O_T, o); // A | B
-      o += D::O_T - D::O_A;
-      for (int i = 0; i < n; i++)
-        for (int j = 0; j < n; j++)
-          *o++ = raw[D::q_off(i, j)];
-      for (int i = 0; i < n; i++)
-        for (int j = 0; j < m; j++)
-          *o++ = raw[D::s_off(i, j)];
-      for (int i = 0; i < m; i++)
-        for (int j = 0; j < m; j++)
-          *o++ = raw[D::r_off(i, j)];
-      std::copy(raw.begin() + D::O_C, raw.begin() + D::O_vpd + D::NC, o);
-    });
+    if (!h || !out)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { h->e->debug_lq(inst, t, out); });
   }
   int smpc_debug_get_steps(smpc_handle * h, double * dxs, double * dus)
   {
-    if (h && h->full)
-      return guarded([&] { h->full->debug_steps(dxs, dus); });
-    if (h && h->cent)
-      return guarded([&] {
-        auto & e = *h->cent;
-        e.get_linear(e.bufs().dxs, (size_t)e.B * (e.H + 1) * 9, dxs);
-        e.get_linear(e.bufs().dus, (size_t)e.B * e.H * e.nu, dus);
-      });
-    return guarded([&] {
-      auto & e = *h->eng;
-      e.get_linear(e.buf.dxs, (size_t)e.B * (e.H + 1) * DimsGo2::NDX, dxs);
-      e.get_linear(e.buf.dus, (size_t)e.B * e.H * DimsGo2::NU, dus);
-    });
+    if (!h || !dxs || !dus)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { h->e->debug_steps(dxs, dus); });
   }
   int smpc_debug_get_terminal(smpc_handle * h, int inst, double * QN, double * qN)
   {
-    if (h && h->full)
-      return guarded([&] { h->full->debug_terminal(inst, QN, qN); });
-    if (h && h->cent)
-      return fail(SMPC_ERR_INVALID, KINO_ONLY);
-    if (!h || inst < 0 || inst >= h->eng->B)
-      return fail(SMPC_ERR_INVALID, "instance index out of range");
-    return guarded([&] {
-      auto & e = *h->eng;
-      e.get_linear(e.buf.QN + (size_t)inst * DimsGo2::NDX * DimsGo2::NDX, DimsGo2::NDX * DimsGo2::NDX, QN);
-      e.get_linear(e.buf.qN + (size_t)inst * DimsGo2::NDX, DimsGo2::NDX, qN);
-    });
+    if (!h || !QN || !qN)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { h->e->debug_terminal(inst, QN, qN); });
   }
   int smpc_debug_get_phase_cycles(smpc_handle * h, double * out64)
   {
-    if (h && h->full)
-      return guarded([&] {
-        if (!h->full->phase_cycles(out64))
-          throw std::runtime_error("phase timers are off (set SMPC_PHASE_PROFILE=1 before smpc_create_fulldynamics)");
-      });
-    if (h && h->cent && h->cent->bufs().dbg)
-      return guarded([&] { h->cent->get_linear(h->cent->bufs().dbg, 64, out64); });
-    if (!h || h->cent || !h->eng->buf.dbg)
-      return fail(SMPC_ERR_INVALID, "phase timers are off (set SMPC_PHASE_PROFILE=1 before smpc_create)");
-    return guarded([&] { h->eng->get_linear(h->eng->buf.dbg, 64, out64); });
+    if (!h || !out64)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { h->e->phase_cycles(out64); });
   }
   int smpc_set_profiling(smpc_handle * h, int en)
   {
-    if (h->full)
-      h->full->profiling = en != 0;
-    else if (h->cent)
-      h->cent->profiling = en != 0;
-    else
-      h->eng->profiling = en != 0;
+    if (!h)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    h->e->profiling = en != 0;
     return SMPC_OK;
   }
   int smpc_kernel_time_slots(void) { return KID_N; }
+  // centroidal handle: slot 0 = front-end kernel, slot 1 = the fused control-step kernel (6-D feet: recede, then deriv / riccati / forward /
+  // line search in slots 2 .. 5), 0 in the slots behind its CentKernelId
   int smpc_get_kernel_times_n(smpc_handle * h, double * ms, long * calls, int n)
   {
     if (!h || !ms || !calls || n < 0)
       return fail(SMPC_ERR_INVALID, "null argument");
-    const int m = n < KID_N ? n : (int)KID_N;
-    if (h->full)
-      return guarded([&] {
-        h->full->collect_profile();
-        for (int i = 0; i < m; i++)
-        {
-          ms[i] = h->full->kernel_ms[i];
-          calls[i] = h->full->kernel_calls[i];
-        }
-      });
-    if (h->cent)
-      return guarded([&] {
-        // centroidal handle: slot 0 = front-end kernel, slot 1 = the fused control-step kernel (6-D feet: recede, then deriv / riccati / forward /
-        // line search in slots 2 .. 5)
-        h->cent->collect_profile();
-        for (int i = 0; i < m; i++)
-        {
-          ms[i] = i < CKID_N ? h->cent->kernel_ms[i] : 0.0;
-          calls[i] = i < CKID_N ? h->cent->kernel_calls[i] : 0;
-        }
-      });
     return guarded([&] {
-      h->eng->collect_profile();
-      for (int i = 0; i < m; i++)
+      h->e->collect_profile();
+      for (int i = 0; i < n && i < KID_N; i++)
       {
-        ms[i] = h->eng->kernel_ms[i];
-        calls[i] = h->eng->kernel_calls[i];
+        ms[i] = h->e->kernel_ms[i];
+        calls[i] = h->e->kernel_calls[i];
       }
     });
   }
@@ -1095,43 +750,17 @@ extern "C"
   int smpc_get_kernel_times(smpc_handle * h, double * ms, long * calls) { return smpc_get_kernel_times_n(h, ms, calls, KID_N); }
   int smpc_reset_kernel_times(smpc_handle * h)
   {
-    if (h->full)
-      return guarded([&] {
-        h->full->collect_profile();
-        for (int i = 0; i < KID_N; i++)
-        {
-          h->full->kernel_ms[i] = 0;
-          h->full->kernel_calls[i] = 0;
-        }
-      });
-    if (h->cent)
-      return guarded([&] {
-        h->cent->collect_profile();
-        for (int i = 0; i < CKID_N; i++)
-        {
-          h->cent->kernel_ms[i] = 0;
-          h->cent->kernel_calls[i] = 0;
-        }
-      });
-    return guarded([&] {
-      h->eng->collect_profile();
-      for (int i = 0; i < KID_N; i++)
-      {
-        h->eng->kernel_ms[i] = 0;
-        h->eng->kernel_calls[i] = 0;
-      }
-    });
+    if (!h)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { h->e->reset_profile(); });
   }
   int smpc_update_internal_data(smpc_handle * h, const double * X, double * feet, double * com, double * hg, double * centroidal_state)
   {
     if (!h || !X)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->update_internal_data(X, feet, com, hg, centroidal_state); });
-    if (h->cent)
-      return guarded([&] { h->cent->update_internal_data(X, feet, com, hg, centroidal_state); });
-    return guarded([&] { h->eng->update_internal_data(X, feet, com, hg, centroidal_state); });
+    return guarded([&] { h->e->update_internal_data(X, feet, com, hg, centroidal_state); });
   }
+  // (a full-dynamics handle: its own robot, 3-D or 6-D contacts, Kp / Kd of force_size entries)
   int smpc_full_forward_dynamics(
     smpc_handle * h, int n, const double * X, const double * tau, const unsigned * contact_mask, const double * Kp,
     const double * Kd, double prox_accuracy, double prox_mu, int prox_max_iter, double * a_out, double * lambda_out,
@@ -1139,36 +768,23 @@ extern "C"
   {
     if (!h || !X || !tau || !contact_mask || !a_out || !lambda_out)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full) // full-dynamics handle: its own robot, 3-D or 6-D contacts (Kp / Kd: force_size entries)
-      return guarded([&] {
-        h->full->full_forward_dynamics(n, X, tau, contact_mask, Kp, Kd, prox_accuracy, prox_mu, prox_max_iter, a_out, lambda_out, iters_out, kernel_ms);
-      });
-    if (!h->eng)
-      return fail(SMPC_ERR_INVALID, "smpc_full_forward_dynamics needs a kinodynamics or a full-dynamics handle (they carry the multibody model)");
     return guarded([&] {
-      h->eng->full_forward_dynamics(n, X, tau, contact_mask, Kp, Kd, prox_accuracy, prox_mu, prox_max_iter, a_out, lambda_out,
-                                    iters_out, kernel_ms);
+      h->e->full_forward_dynamics(n, X, tau, contact_mask, Kp, Kd, prox_accuracy, prox_mu, prox_max_iter, a_out, lambda_out, iters_out, kernel_ms);
     });
   }
   int smpc_riccati_feedback(smpc_handle * h, double delay, const double * X_meas, double * u_out)
   {
     if (!h || !X_meas || !u_out)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full)
-      return guarded([&] { h->full->riccati_feedback(delay, X_meas, u_out); });
-    if (h->cent)
-      return guarded([&] { h->cent->interpolate(delay, 2, X_meas, nullptr, nullptr, nullptr, u_out); });
-    return guarded([&] { h->eng->riccati_feedback(delay, X_meas, u_out); });
+    return guarded([&] { h->e->riccati_feedback(delay, X_meas, u_out); });
   }
+  // full-dynamics handle: force_out [B][nfeet][force_size] = interpolated MPC::getContactForces; centroidal handle: x_out [B][9], acc_out = state
+  // derivative [B][9], force_out [B][3 nfeet]
   int smpc_interpolate(smpc_handle * h, double delay, int knots, double * x_out, double * acc_out, double * force_out)
   {
     if (!h)
       return fail(SMPC_ERR_INVALID, "null argument");
-    if (h->full) // full-dynamics handle: force_out [B][nfeet][force_size] = interpolated MPC::getContactForces
-      return guarded([&] { h->full->interpolate(delay, knots, x_out, acc_out, force_out); });
-    if (h->cent) // centroidal handle: x_out [B][9], acc_out = state derivative [B][9], force_out [B][3 nfeet]
-      return guarded([&] { h->cent->interpolate(delay, knots, nullptr, x_out, acc_out, force_out, nullptr); });
-    return guarded([&] { h->eng->interpolate(delay, knots, x_out, acc_out, force_out); });
+    return guarded([&] { h->e->interpolate(delay, knots, x_out, acc_out, force_out); });
   }
   int smpc_interpolate_knots(int kind, double delay, double timestep, const double * knots, int n, int dim, double * out, int device_id)
   {
@@ -1363,9 +979,7 @@ extern "C"
     if (!h || !q || !v || !a || !contact || !f)
       return fail(SMPC_ERR_INVALID, "null argument");
     IdEngineBase * e = reinterpret_cast<IdEngineBase *>(h);
-    unsigned mask = 0;
-    for (int k = 0; k < e->nf; k++)
-      mask |= contact[k] ? (1u << k) : 0u;
+    const unsigned mask = contact_bits(contact, e->nf);
     return guarded([&] { e->set_target(instance, q, v, a, mask, f); });
   }
   int smpc_id_set_targets(smpc_id_handle * h, const double * Q, const double * V, const double * A, const uint8_t * contact, const double * F)
@@ -1380,9 +994,7 @@ extern "C"
     if (!h || !com || !vcom || !feet_p || !feet_v || !contact || !f)
       return fail(SMPC_ERR_INVALID, "null argument");
     IdEngineBase * e = reinterpret_cast<IdEngineBase *>(h);
-    unsigned mask = 0;
-    for (int k = 0; k < e->nf; k++)
-      mask |= contact[k] ? (1u << k) : 0u;
+    const unsigned mask = contact_bits(contact, e->nf);
     return guarded([&] { e->set_target_centroidal(instance, com, vcom, feet_p, feet_v, mask, f); });
   }
   int smpc_id_set_targets_centroidal(smpc_id_handle * h, const double * COM, const double * VCOM, const double * FEET_P, const double * FEET_V,
@@ -1436,62 +1048,31 @@ extern "C"
     if (!id || !mpc)
       return fail(SMPC_ERR_INVALID, "null argument");
     IdEngineBase * e = reinterpret_cast<IdEngineBase *>(id);
-    if (mpc->cent)
-    { // centroidal MPC -> CentroidalID (examples/talos_centroidal.py:218-243)
-      double *com, *vcom, *fp, *fv, *x, *a, *f;
-      e->centroidal_target_buffers(&com, &vcom, &fp, &fv);
-      if (!com)
-        return fail(SMPC_ERR_INVALID, "a centroidal MPC handle feeds a CentroidalID controller");
-      if (e->B != mpc->cent->B || e->nf != mpc->cent->nf || e->nv != mpc->cent->nv_mb || e->nfw * e->nf != mpc->cent->nu)
-        return fail(SMPC_ERR_INVALID, "the controller and the MPC must hold the same batch of the same robot");
-      return guarded([&] {
-        e->target_buffers(&x, &a, &f);
-        e->set_mask_all(mpc->cent->contact_mask(0));
-        const bool shared = e->solve_stream() == mpc->cent->stream; // (one in-order queue: nothing to order)
-        if (!shared)
-          e->wait();
-        mpc->cent->interpolate_device_id(delay, knots, com, vcom, fp, fv, f);
-        if (!shared)
-          mpc->cent->wait_stream(e->solve_stream());
-      });
-    }
-    {
-      double *com, *vcom, *fp, *fv;
-      e->centroidal_target_buffers(&com, &vcom, &fp, &fv);
-      if (com)
-        return fail(SMPC_ERR_INVALID, "a kinodynamics MPC handle feeds a KinodynamicsID controller");
-    }
-    if (mpc->full)
-    { // kinodynamics OCP of a robot with flat feet (dense engine) or a full-dynamics OCP -> KinodynamicsID: states, accelerations, contact forces
-      FullEngineBase & fe = *mpc->full;
-      if (e->B != fe.B || e->nq != fe.dims[0] || e->nv != fe.dims[1] || e->nf != fe.dims[6] || e->nfw != fe.force_size)
-        return fail(SMPC_ERR_INVALID, "the controller and the MPC must hold the same batch of the same robot");
-      return guarded([&] {
-        double *x, *a, *f;
-        e->target_buffers(&x, &a, &f);
-        e->set_mask_all(fe.contact_mask(0));
-        const bool shared = e->solve_stream() == fe.stream;
-        if (!shared)
-          e->wait();
-        fe.interpolate_device(delay, knots, x, a, f);
-        if (!shared)
-          fe.wait_stream(e->solve_stream());
-      });
-    }
-    if (!mpc->eng)
-      return fail(SMPC_ERR_INVALID, "smpc_id_set_targets_from_mpc needs an MPC handle");
-    if (e->B != mpc->eng->B || e->nq != DimsGo2::NQ || e->nv != DimsGo2::NV)
+    MpcEngineBase & m = *mpc->e;
+    double *com, *vcom, *fp, *fv;
+    e->centroidal_target_buffers(&com, &vcom, &fp, &fv);
+    // centroidal MPC -> CentroidalID (examples/talos_centroidal.py:218-243); kinodynamics OCP (either engine) or full-dynamics OCP ->
+    // KinodynamicsID: states, accelerations, contact forces
+    if (m.centroidal() && !com)
+      return fail(SMPC_ERR_INVALID, "a centroidal MPC handle feeds a CentroidalID controller");
+    if (!m.centroidal() && com)
+      return fail(SMPC_ERR_INVALID, "a kinodynamics MPC handle feeds a KinodynamicsID controller");
+    if (e->B != m.B || e->nv != m.dims[1] || e->nf != m.dims[6]
+        || (m.centroidal() ? e->nfw * e->nf != m.dims[4] : (e->nq != m.dims[0] || e->nfw != m.force_size)))
       return fail(SMPC_ERR_INVALID, "the controller and the MPC must hold the same batch of the same robot");
     return guarded([&] {
       double *x, *a, *f;
       e->target_buffers(&x, &a, &f);
-      e->set_mask_all(mpc->eng->contact_mask(0));
-      const bool shared = e->solve_stream() == mpc->eng->stream; // (one in-order queue: nothing to order)
+      e->set_mask_all(m.contact_mask(0));
+      const bool shared = e->solve_stream() == m.stream; // (one in-order queue: nothing to order)
       if (!shared)
         e->wait(); // (the previous solve has read its targets)
-      mpc->eng->interpolate_device(delay, knots, x, a, f);
+      if (m.centroidal())
+        m.interpolate_device_id(delay, knots, com, vcom, fp, fv, f);
+      else
+        m.interpolate_device(delay, knots, x, a, f);
       if (!shared)
-        mpc->eng->wait_stream(e->solve_stream()); // the next solve starts after the targets are written
+        m.wait_stream(e->solve_stream()); // the next solve starts after the targets are written
     });
   }
   int smpc_id_share_stream(smpc_id_handle * id, smpc_handle * mpc)
@@ -1501,29 +1082,18 @@ extern "C"
     IdEngineBase * e = reinterpret_cast<IdEngineBase *>(id);
     if (!mpc)
       return guarded([&] { e->adopt_stream(e->solve_stream(), true); });
-    if ((mpc->full ? mpc->full->device_id : (mpc->cent ? mpc->cent->device_id : mpc->eng->device_id)) != e->device())
+    if (mpc->e->device_id != e->device())
       return fail(SMPC_ERR_INVALID, "smpc_id_share_stream: the controller and the MPC handle live on different devices");
-    return guarded([&] { e->adopt_stream(mpc->full ? mpc->full->stream : (mpc->cent ? mpc->cent->stream : mpc->eng->stream), false); });
+    return guarded([&] { e->adopt_stream(mpc->e->stream, false); });
   }
+  // (a full-dynamics handle: its own robot and contact model, Kp / Kd of force_size entries)
   int smpc_sim_step_device(smpc_handle * h, double * X_device, const double * tau_device, const uint8_t * contact, const double * Kp, const double * Kd, double dt)
   {
     if (!h || !X_device || !tau_device || !contact)
       return fail(SMPC_ERR_INVALID, "null argument");
     if (!(dt > 0.0))
       return fail(SMPC_ERR_INVALID, "dt must be positive");
-    if (h->full)
-    { // full-dynamics handle: its own robot and contact model (Kp / Kd: force_size entries)
-      unsigned mask = 0;
-      for (int k = 0; k < h->full->dims[6]; k++)
-        mask |= contact[k] ? (1u << k) : 0u;
-      return guarded([&] { h->full->sim_step_device(X_device, tau_device, mask, Kp, Kd, dt); });
-    }
-    if (!h->eng)
-      return fail(SMPC_ERR_INVALID, "smpc_sim_step_device needs a kinodynamics or a full-dynamics handle (they carry the multibody model)");
-    unsigned mask = 0;
-    for (int k = 0; k < DimsGo2::NF; k++)
-      mask |= contact[k] ? (1u << k) : 0u;
-    return guarded([&] { h->eng->sim_step_device(X_device, tau_device, mask, Kp, Kd, dt); });
+    return guarded([&] { h->e->sim_step_device(X_device, tau_device, contact_bits(contact, h->e->dims[6]), Kp, Kd, dt); });
   }
   double * smpc_id_get_x_device(smpc_id_handle * h) { return h ? reinterpret_cast<IdEngineBase *>(h)->x_device() : nullptr; }
   int smpc_id_debug_get(smpc_id_handle * h, int what, double * out)

@@ -39,6 +39,7 @@ namespace smpc
     CKID_TRIAL,   //   6-D feet: stage merits of the line-search candidates (cent6_trial_body)
     CKID_N
   };
+  static_assert(CKID_N <= KID_N, "the kernel-time slots of MpcEngineBase hold every centroidal kernel");
 
   template <class DK>
   struct cent_is_full_dims
@@ -62,71 +63,12 @@ namespace smpc
     double *parts0 = nullptr, *partsT = nullptr, *xdotT = nullptr; // (Cent6Args, smpc_cent6_kernels.h)
   };
 
-  // what the C ABI needs from a centroidal engine of any robot shape / foot type
-  struct CentEngineBase
-  {
-    int B = 0, H = 0, R = 0, head = 0;
-    int nu = 0, nc = 0, nf = 0, nq_mb = 0, nv_mb = 0;
-    int device_id = 0; // every entry point makes this the current device first
-    GaitTimer timer;
-    stream_t stream;
-    double x_reference[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int cold_iters = 0;
-    std::vector<double> cold_trace;
-    bool profiling = false;
-    double kernel_ms[CKID_N] = {0};
-    long kernel_calls[CKID_N] = {0};
-    virtual ~CentEngineBase() {}
-    virtual const CentBuffersBase & bufs() const = 0;
-    virtual void collect_profile() = 0;
-    virtual void generate_cycle_horizon(const unsigned char * cs, int n) = 0;
-    virtual void switch_to_walk(const double * v6) = 0;
-    virtual void switch_to_stand() = 0;
-    virtual void set_velocity_base_batched(const double * V) = 0;
-    virtual void iterate_device(const double * Xd) = 0;
-    virtual void iterate_host(const double * X) = 0;
-    virtual void sync() = 0;
-    virtual void set_stage_reference(int t, int what, const double * v, int n) = 0;
-    virtual void get_stage_reference(int t, int what, double * v, int n) = 0;
-    virtual void set_reference_pose(int t, int foot, const double * p3) = 0;
-    virtual void get_reference_pose(int t, int foot, int inst, double * p3) = 0;
-    virtual void set_reference_rotation(int t, int foot, const double * R9) = 0;
-    virtual void get_reference_rotation(int t, int foot, double * R9) = 0;
-    virtual unsigned contact_mask(int t) const = 0;
-    virtual void update_internal_data(const double * X, double * feet, double * com, double * hg, double * cstate) = 0;
-    virtual void interpolate_device_id(double delay, int knots, double * com, double * vcom, double * fp, double * fv, double * f) = 0;
-    virtual void wait_stream(stream_t other) = 0;
-    virtual void interpolate(double delay, int knots, const double * X_meas, double * x_out, double * xdot_out, double * f_out, double * u_out) = 0;
-    virtual size_t state_io(StateIO & io) = 0;
-    virtual void get_K(double * out, bool all) = 0;
-    virtual void state_derivatives(double * out) = 0; // xdot of every stage at the last solve's iterate, [B][H][9] (device, handle's stream)
-    void get_ring(const double * src, int n, int count, double * out)
-    {
-      set_device(device_id);
-      stream_sync(stream);
-      std::vector<double> tmp((size_t)B * R * n);
-      d2h(tmp.data(), src, tmp.size() * sizeof(double), stream);
-      stream_sync(stream);
-      for (int b = 0; b < B; b++)
-        for (int t = 0; t < count; t++)
-          std::memcpy(out + ((size_t)b * count + t) * n, tmp.data() + ((size_t)b * R + ring_slot(head, t, R)) * n, n * sizeof(double));
-    }
-    void get_linear(const double * src, size_t n, double * out)
-    {
-      set_device(device_id);
-      stream_sync(stream);
-      d2h(out, src, n * sizeof(double), stream);
-      stream_sync(stream);
-    }
-  };
-
   // DK: Dims of the multibody robot (front-end FK; a FullDims selects the front end of the dense stage kernels), DC: CentDims
   template <class DK, class DC>
-  class CentEngine : public CentEngineBase
+  class CentEngine : public MpcEngineBase
   {
   public:
     CentBuffers<DC> buf;
-    const CentBuffersBase & bufs() const override { return buf; }
     Cent6Extra<DC, DC::FS> x6; // 6-D feet: knots, dense gains, terminal node, merit partials
     CentSplitBuffers sbuf;     // point feet: hand-over records of the kernel pipeline (smpc_cent_split.h)
     bool fused = false;        // point feet: SMPC_CENT_FUSED=1 runs the one-kernel control step (cross-check)
@@ -141,21 +83,16 @@ namespace smpc
     std::vector<event_t> part_event;   // [nparts - 1] completion of a part, [nparts] stagger events
     event_t ev_fork{};
     Buffers<DK> fk; // only .model is used (front-end kernel)
-    HostMpcSettings ms;
     std::vector<CentStage<DC>> horizon, cycle;
     CentStage<DC> standing;
-    bool walking = true;
-    double velocity_base[6] = {0, 0, 0, 0, 0, 0};
     double com_ref_member[3] = {0, 0, 0}; // CentroidalOCP::com_ref_ (last setPoseBase)
     double mass;
-    std::vector<double> x_model_ref;
     UploadRing stage_ring; // pinned staging of the per-step stage table
     double *X_dev = nullptr, *cstate_dev = nullptr, *feet_dev = nullptr;
-    std::vector<std::pair<int, std::pair<event_t, event_t>>> pending_events;
     static constexpr double ARMIJO_C1 = 1e-4, REG_INIT = 1e-9, REG_MIN = 1e-10, REG_MAX = 1e9, REG_INC = 10.0, REG_DEC = 1.0 / 3.0, STALL_REL = 1e-9;
 
     CentEngine(const smpc_robot_model * rm, const HostCentSettings & cs, const HostMpcSettings & ms_, int batch, double gravity_arg, int device)
-    : ms(ms_)
+    : MpcEngineBase(ms_, batch, device)
     {
       AllocScope ctor_scope; // (a throw below releases what was allocated so far: smpc_alloc_scope.h)
       if (batch <= 0)
@@ -171,17 +108,11 @@ namespace smpc
         throw std::runtime_error("horizon must have at least 2 stages");
       if (DC::FS == 6 && ms.T + 1 > 256) // (before anything is allocated: a constructor that throws runs no destructor)
         throw std::runtime_error("centroidal OCP with 6-D feet: at most 255 stages");
-      device_id = device;
-      set_device(device);
-      stream = stream_create();
-      B = batch;
-      H = ms.T;
-      R = H + 1;
-      nu = DC::NU;
-      nc = DC::NC;
-      nf = DC::NF;
-      nq_mb = DK::NQ;
-      nv_mb = DK::NV;
+      open_stream();
+      force_size = DC::FS;
+      const int dd[8] = {DK::NQ, DK::NV, 9, 9, DC::NU, DC::NC, DC::NF, H}; // nq, nv of the robot; the problem state is [com; h_lin; h_ang]
+      std::copy(dd, dd + 8, dims);
+      x_reference.assign(9, 0.0);
       mass = rm->total_mass;
       // ---- models ----
       std::vector<DevModel<DK>> hk(1);
@@ -229,7 +160,7 @@ namespace smpc
       buf.dlams = dalloc(BR * 9);
       buf.foot = dalloc(BH * DC::NF * 3);
       buf.ftraj = dalloc((size_t)B * DC::NF * 6);
-      buf.vbase = dalloc((size_t)B * 6);
+      buf.vbase = vbase_dev = dalloc((size_t)B * 6);
       buf.vref = dalloc(BR * 6);
       buf.gains = dalloc(BH * DC::G_STRIDE);
       if constexpr (DC::FS == 6)
@@ -267,11 +198,11 @@ namespace smpc
           nparts = pe ? std::atoi(pe) : (B >= 1024 ? 2 : 1);
           if (nparts < 1 || nparts > 8 || B < 64 * nparts)
             nparts = 1;
-          ev_fork = event_create();
+          ev_fork = side.event();
           for (int p = 1; p < nparts; p++)
-            part_stream.push_back(stream_create());
+            part_stream.push_back(side.stream());
           for (int p = 0; p < 2 * nparts; p++)
-            part_event.push_back(event_create());
+            part_event.push_back(side.event());
         }
       }
       buf.scal = dalloc((size_t)B * SC_N);
@@ -306,18 +237,8 @@ namespace smpc
     ~CentEngine()
     {
       for (double * p : {buf.xs, buf.us, buf.vs, buf.lams, buf.vs_e, buf.lams_e, buf.dxs, buf.dus, buf.dvs, buf.dlams, buf.foot, buf.ftraj, buf.vbase, buf.vref, buf.gains, buf.scal, buf.xdot01,
-                         buf.zeros, buf.dbg, X_dev, cstate_dev, feet_dev, stage_out, sbuf.rec, sbuf.term})
+                         buf.zeros, buf.dbg, X_dev, cstate_dev, feet_dev, sbuf.rec, sbuf.term})
         dev_free(p);
-      if (ev_handoff_valid)
-        event_destroy(ev_handoff);
-      if (!part_event.empty())
-      {
-        event_destroy(ev_fork);
-        for (auto & e : part_event)
-          event_destroy(e);
-        for (auto & st : part_stream)
-          stream_destroy(st);
-      }
       if constexpr (DC::FS == 6)
       {
         for (double * p : {x6.sb.lq, x6.sb.QN, x6.sb.qN, x6.parts0, x6.partsT, x6.xdotT})
@@ -327,44 +248,6 @@ namespace smpc
       dev_free(buf.stages);
       dev_free(buf.model);
       dev_free(fk.model);
-      stream_destroy(stream);
-    }
-    CentEngine(const CentEngine &) = delete;
-    CentEngine & operator=(const CentEngine &) = delete;
-
-    template <class Args, void (*Body)(const Args &, int), int NT, int MINW = 1>
-    void timed_launch(int kid, int grid, const Args & a, bool aux = false, const stream_t * on = nullptr)
-    {
-      set_device(device_id);
-      const stream_t st = on ? *on : stream;
-      event_t e0{}, e1{};
-      if (profiling)
-      {
-        e0 = event_create();
-        e1 = event_create();
-        event_record(e0, st);
-      }
-      if (aux)
-        launch<Args, Body, NT, MINW, 1>(grid, st, a);
-      else
-        launch<Args, Body, NT, MINW, 0>(grid, st, a);
-      if (profiling)
-      {
-        event_record(e1, st);
-        pending_events.push_back({kid, {e0, e1}});
-      }
-      kernel_calls[kid]++;
-    }
-    void collect_profile() override
-    {
-      stream_sync(stream);
-      for (auto & pe : pending_events)
-      {
-        kernel_ms[pe.first] += event_elapsed_ms(pe.second.first, pe.second.second);
-        event_destroy(pe.second.first);
-        event_destroy(pe.second.second);
-      }
-      pending_events.clear();
     }
 
     void upload_stages()
@@ -601,37 +484,6 @@ namespace smpc
         cycle.push_back(s);
       }
     }
-    void upload_velocity(const double * V, bool broadcast)
-    {
-      set_device(device_id);
-      std::vector<double> h((size_t)B * 6);
-      for (int b = 0; b < B; b++)
-        for (int i = 0; i < 6; i++)
-          h[(size_t)b * 6 + i] = broadcast ? V[i] : V[(size_t)b * 6 + i];
-      h2d(buf.vbase, h.data(), h.size() * sizeof(double), stream);
-      stream_sync(stream);
-    }
-    void switch_to_walk(const double * v6) override
-    {
-      walking = true;
-      for (int i = 0; i < 6; i++)
-        velocity_base[i] = v6[i];
-      upload_velocity(v6, true);
-    }
-    void switch_to_stand() override
-    {
-      walking = false;
-      for (int i = 0; i < 6; i++)
-        velocity_base[i] = 0.0;
-      upload_velocity(velocity_base, true);
-    }
-    void set_velocity_base_batched(const double * V) override
-    {
-      for (int i = 0; i < 6; i++)
-        velocity_base[i] = V[i];
-      upload_velocity(V, false);
-    }
-
     void iterate_device(const double * Xd) override
     {
       ref_rot.reset(); // (every control step rewrites every stage's reference pose with the identity rotation: src/mpc.cpp:303-309)
@@ -700,24 +552,6 @@ namespace smpc
     }
     // ---- per-stage references (OCPHandler setters / getters of the centroidal OCP, reference src/centroidal-dynamics.cpp:
     //      120-304), broadcast over the batch ----
-    void check_stage(int t) const
-    {
-      if (t < 0 || t >= H)
-        throw std::runtime_error("Stage index exceeds stage vector size");
-    }
-    void fill_strided(double * base, size_t stride, int count, const double * v, int n)
-    {
-      set_device(device_id);
-      FillStridedArgs fa;
-      fa.base = base;
-      fa.stride = stride;
-      fa.count = count;
-      fa.n = n;
-      for (int i = 0; i < n; i++)
-        fa.v[i] = v[i];
-      launch<FillStridedArgs, fill_strided_body, 64>((count + 63) / 64, stream, fa);
-      stream_sync(stream);
-    }
     // what: 0 = control target (nu); 1 = reference state as get / setReferenceState define it: [com_ref; v_lin; v_ang]
     // (setReferenceState = setPoseBase + setVelocityBase, which stores the momenta m v; getReferenceState divides by m)
     void set_stage_reference(int t, int what, const double * v, int n) override
@@ -766,8 +600,7 @@ namespace smpc
     void set_reference_pose(int t, int foot, const double * p3) override
     {
       check_stage(t);
-      if (foot < 0 || foot >= DC::NF)
-        throw std::runtime_error("unknown end effector");
+      check_foot(foot);
       ref_rot.set(t, foot, nullptr); // (a translation: identity rotation)
       fill_strided(buf.foot + ((size_t)t * DC::NF + foot) * 3, (size_t)H * DC::NF * 3, B, p3, 3);
     }
@@ -777,21 +610,6 @@ namespace smpc
       if (foot < 0 || foot >= DC::NF || inst < 0 || inst >= B)
         throw std::runtime_error("unknown end effector or instance");
       get_linear(buf.foot + (((size_t)inst * H + t) * DC::NF + foot) * 3, 3, p3);
-    }
-    RefRotations ref_rot; // rotations of the foot reference placements: API state (smpc_model.h)
-    void set_reference_rotation(int t, int foot, const double * R9) override
-    {
-      check_stage(t);
-      if (foot < 0 || foot >= DC::NF)
-        throw std::runtime_error("unknown end effector");
-      ref_rot.set(t, foot, R9);
-    }
-    void get_reference_rotation(int t, int foot, double * R9) override
-    {
-      check_stage(t);
-      if (foot < 0 || foot >= DC::NF)
-        throw std::runtime_error("unknown end effector");
-      ref_rot.get(t, foot, R9);
     }
     unsigned contact_mask(int t) const override
     {
@@ -854,20 +672,14 @@ namespace smpc
       ia.mass = mass;
       launch<CentInterpArgs<DC>, cent_interp_body<DC>, 64>(B, stream, ia);
     }
-    void wait_stream(stream_t other) override
+    bool centroidal() const override { return true; }
+    // smpc_interpolate on a centroidal handle: x_out [B][9], acc_out = state derivative [B][9], force_out [B][3 nfeet]
+    void interpolate(double delay, int knots, double * x_out, double * acc_out, double * f_out) override
     {
-      set_device(device_id);
-      if (!ev_handoff_valid)
-      {
-        ev_handoff = event_create();
-        ev_handoff_valid = true;
-      }
-      event_record(ev_handoff, stream);
-      stream_wait_event(other, ev_handoff);
+      interpolate_cent(delay, knots, nullptr, x_out, acc_out, f_out, nullptr);
     }
-    event_t ev_handoff{};
-    bool ev_handoff_valid = false;
-    void interpolate(double delay, int knots, const double * X_meas, double * x_out, double * xdot_out, double * f_out, double * u_out) override
+    void riccati_feedback(double delay, const double * X, double * u_out) override { interpolate_cent(delay, 2, X, nullptr, nullptr, nullptr, u_out); }
+    void interpolate_cent(double delay, int knots, const double * X_meas, double * x_out, double * xdot_out, double * f_out, double * u_out)
     {
       if (knots < 2 || knots > H + 1)
         throw std::runtime_error("interpolate: knots must be in [2, horizon + 1]");
@@ -914,7 +726,7 @@ namespace smpc
       io.pod(head);
       io.pod(walking);
       io.host(velocity_base, sizeof(velocity_base));
-      io.host(x_reference, sizeof(x_reference));
+      io.host(x_reference.data(), 9 * sizeof(double));
       io.host(com_ref_member, sizeof(com_ref_member));
       io.vec(horizon);
       io.vec(cycle);
@@ -951,27 +763,8 @@ namespace smpc
       a.out = out;
       launch<XdotArgs<CentBuffers<DC>>, xdot_all_body<DC, CentBuffers<DC>, XD_CENT>, 64>(xdot_grid(XD_CENT, B, H), stream, a);
     }
-    void sync() override
-    {
-      set_device(device_id);
-      stream_sync(stream);
-    }
-
-    double * stage_out = nullptr;
-    size_t stage_out_bytes = 0;
-    double * staging(size_t bytes)
-    {
-      set_device(device_id);
-      if (bytes > stage_out_bytes)
-      {
-        stream_sync(stream);
-        dev_free(stage_out);
-        stage_out = (double *)dev_alloc(bytes);
-        stage_out_bytes = bytes;
-      }
-      return stage_out;
-    }
-    void get_K(double * out, bool all) override
+    size_t xdot_doubles() const override { return (size_t)B * H * 9; }
+    void get_K(double * out, bool all)
     {
       const int nt = all ? H : 1;
       const size_t n = (size_t)B * nt * DC::NU * 9;
@@ -983,6 +776,47 @@ namespace smpc
       launch<CentGainsOutArgs<DC>, cent_gains_out_body<DC>, 64>(B * nt, stream, ga);
       d2h(out, dev, n * sizeof(double), stream);
       stream_sync(stream);
+    }
+    void get_output(Output what, double * out) override
+    {
+      switch (what)
+      {
+      case OUT_XS:
+        return get_ring(buf.xs, 9, H + 1, out);
+      case OUT_US:
+        return get_ring(buf.us, DC::NU, H, out);
+      case OUT_K0:
+        return get_K(out, false);
+      case OUT_KS:
+        return get_K(out, true);
+      case OUT_VS:
+        return get_ring(buf.vs, DC::NC, H, out);
+      case OUT_LAMS:
+        return get_lams(buf.lams, 9, out);
+      case OUT_XDOT01:
+        return get_linear(buf.xdot01, (size_t)B * 18, out);
+      case OUT_FOOT_REFS:
+        return get_linear(buf.foot, (size_t)B * H * DC::NF * 3, out);
+      case OUT_INFO:
+        return get_linear(buf.scal, (size_t)B * SC_N, out);
+      default:
+        throw InvalidCall("smpc_get_contact_forces needs a full-dynamics handle (the other problems carry the forces in us)");
+      }
+    }
+    void set_early_exit(bool) override
+    {
+      throw InvalidCall("smpc_set_early_exit_on_tol: kinodynamics and full-dynamics handles (the centroidal step is one fused kernel)");
+    }
+    void debug_steps(double * dxs, double * dus) override
+    {
+      get_linear(buf.dxs, (size_t)B * (H + 1) * 9, dxs);
+      get_linear(buf.dus, (size_t)B * H * DC::NU, dus);
+    }
+    void phase_cycles(double * out64) override
+    {
+      if (!buf.dbg)
+        throw InvalidCall("phase timers are off (set SMPC_PHASE_PROFILE=1 before smpc_create)");
+      get_linear(buf.dbg, 64, out64);
     }
   };
 } // namespace smpc

@@ -88,7 +88,7 @@ namespace smpc
     double u_ref[D::NU];
     double x_tgt[9]; // [com_ref; h_ref; L_ref]
   };
-  // (the pointers are the same for every foot type: CentBuffersBase is what the C ABI reads through CentEngineBase)
+  // (the pointers are the same for every foot type; kept as the base of CentBuffers because that is its layout in the kernels' argument structs)
   struct CentBuffersBase
   {
     int B = 0, H = 0, R = 0;

@@ -18,6 +18,7 @@
 #ifndef SMPC_DERIV2_MINW
 #define SMPC_DERIV2_MINW 2 // waves per SIMD the register allocation of deriv2_body is capped for (3: measured refusal)
 #endif
+#include "smpc_engine_base.h"
 #include "smpc_riccati_kino.h"
 #include "smpc_kino_deriv2.h"
 #include "smpc_solver_kernels.h"
@@ -41,11 +42,6 @@ namespace smpc
     int force_cone = 0;          // friction-cone rows per foot in contact (3-D feet)
     int land_cstr = 0;           // height of a landing foot pinned to its contact pose
     double mu = 0.8;             // friction coefficient
-  };
-  struct HostMpcSettings
-  {
-    double swing_apex, support_force, TOL, mu_init, timestep;
-    int max_iters, num_threads, T_fly, T_contact, T;
   };
 
   // CoM height at state x from the host copy of a device model (MPC::com0_ at the reference state, reference src/mpc.cpp:93)
@@ -98,170 +94,6 @@ namespace smpc
     bf.com0z = com_height;
     h2d(bf.dcm_ref, x0, 3 * sizeof(double), stream);
   }
-
-  // integer gait bookkeeping (reference src/mpc.cpp:101-132, 220-276)
-  struct GaitTimer
-  {
-    int H = 0, nf = 0;
-    std::vector<std::vector<unsigned char>> states;
-    std::vector<std::vector<int>> takeoff, land;
-    void generate(const unsigned char * cs, int n, int nf_, int H_)
-    {
-      H = H_;
-      nf = nf_;
-      states.clear();
-      const int reps = 1 + H / n; // original + m copies, m = H / n (integer division)
-      for (int r = 0; r < reps; r++)
-        for (int i = 0; i < n; i++)
-          states.emplace_back(cs + (size_t)i * nf, cs + (size_t)(i + 1) * nf);
-      takeoff.assign(nf, {});
-      land.assign(nf, {});
-      const int N = (int)states.size();
-      for (int f = 0; f < nf; f++)
-      {
-        for (int i = 1; i < N; i++)
-        {
-          const bool now = states[i][f], prev = states[i - 1][f];
-          if (!now && prev)
-            takeoff[f].push_back(i + H);
-          if (now && !prev)
-            land[f].push_back(i + H);
-        }
-        if (states[N - 1][f] && !states[0][f])
-          takeoff[f].push_back(N - 1 + H);
-        if (!states[N - 1][f] && states[0][f])
-          land[f].push_back(N - 1 + H);
-      }
-    }
-    void update_timing(bool only_horizon)
-    {
-      for (int f = 0; f < nf; f++)
-      {
-        for (auto * v : {&land[f], &takeoff[f]})
-        {
-          for (int & t : *v)
-            if (!only_horizon || t < H)
-              t -= 1;
-          if (!v->empty() && (*v)[0] < 0)
-            v->erase(v->begin());
-        }
-      }
-    }
-    void recede_cycle()
-    {
-      std::rotate(states.begin(), states.begin() + 1, states.end());
-      const int N = (int)states.size();
-      for (int f = 0; f < nf; f++)
-      {
-        if (!states[N - 1][f] && states[N - 2][f])
-          takeoff[f].push_back(N + H);
-        if (states[N - 1][f] && !states[N - 2][f])
-          land[f].push_back(N + H);
-      }
-      update_timing(false);
-    }
-  };
-
-  enum KernelId
-  {
-    KID_RECEDE = 0,
-    KID_DERIV,
-    KID_RICCATI,
-    KID_FORWARD,
-    KID_TRIAL,
-    KID_SELECT,
-    KID_APPLY,
-    KID_TREE,    // lane-per-problem tree pass (smpc_kino_lane.h) of the full-batch derivative launches
-    KID_TREE_LS, // ... of the full-batch line-search launches (evaluation mode: heads only)
-    KID_N
-  };
-
-  // checkpoint / resume of a handle (smpc_save_state / smpc_load_state): one pass over the state in a fixed order, in one
-  // of three modes (count the bytes, copy out, copy in)
-  struct StateIO
-  {
-    enum Mode
-    {
-      COUNT,
-      SAVE,
-      LOAD
-    } mode;
-    char * buf;
-    size_t cap, pos = 0;
-    stream_t st;
-    StateIO(Mode m, void * b, size_t c, stream_t s) : mode(m), buf((char *)b), cap(c), st(s) {}
-    void need(size_t n) const
-    {
-      if (mode != COUNT && pos + n > cap)
-        throw std::runtime_error(mode == SAVE ? "state buffer too small" : "state buffer truncated");
-    }
-    void host(void * p, size_t n)
-    {
-      need(n);
-      if (mode == SAVE)
-        std::memcpy(buf + pos, p, n);
-      else if (mode == LOAD)
-        std::memcpy(p, buf + pos, n);
-      pos += n;
-    }
-    void dev(void * p, size_t n)
-    {
-      need(n);
-      if (mode == SAVE)
-        d2h(buf + pos, p, n, st);
-      else if (mode == LOAD)
-        h2d(p, buf + pos, n, st);
-      pos += n;
-    }
-    template <class T>
-    void pod(T & v)
-    {
-      host(&v, sizeof(T));
-    }
-    // a value that must be the same in the handle and in the buffer (shape of the problem)
-    void tag(long long v, const char * what)
-    {
-      long long w = v;
-      pod(w);
-      if (mode == LOAD && w != v)
-        throw std::runtime_error(std::string("saved state does not match this handle: ") + what);
-    }
-    template <class T>
-    void vec(std::vector<T> & v)
-    {
-      unsigned long long n = v.size();
-      pod(n);
-      if (mode == LOAD)
-      {
-        if (n * sizeof(T) > cap)
-          throw std::runtime_error("state buffer corrupt");
-        v.resize((size_t)n);
-      }
-      if (n)
-        host(v.data(), (size_t)n * sizeof(T));
-    }
-    void timer(GaitTimer & t)
-    {
-      pod(t.H);
-      pod(t.nf);
-      unsigned long long ns = t.states.size();
-      pod(ns);
-      if (mode == LOAD)
-        t.states.assign((size_t)ns, std::vector<unsigned char>());
-      for (auto & s : t.states)
-        vec(s);
-      if (mode == LOAD)
-      {
-        t.takeoff.assign(t.nf, {});
-        t.land.assign(t.nf, {});
-      }
-      for (int f = 0; f < t.nf; f++)
-      {
-        vec(t.takeoff[f]);
-        vec(t.land[f]);
-      }
-    }
-  };
 
   // kinematic tree, inertias and feet of the robot table -> device model (shared by the kinodynamics engine and the
   // front-end of the centroidal engine)
@@ -332,44 +164,34 @@ namespace smpc
     m.lane_slots = ok ? std::max(nslots, 1) : 0;
   }
 
+  // doubles of the row-major form of a kinodynamics knot (smpc_debug_get_lq)
   template <class D>
-  class KinoEngine
+  constexpr int kino_lq_size()
+  {
+    return (D::O_T - D::O_A) + D::NDX * D::NDX + D::NDX * D::NU + D::NU * D::NU + (D::O_vpd + D::NC - D::O_C);
+  }
+
+  template <class D>
+  class KinoEngine : public MpcEngineBase
   {
   public:
     typedef Dims<D::NJ, D::NF> DD;
     Buffers<D> buf;
-    int B, H, R, head = 0;
-    int device_id = 0; // every entry point makes this the current device first: a process may hold handles on several GPUs
-    HostMpcSettings ms;
     std::vector<StageShared<D>> horizon, cycle;
     StageShared<D> standing;
-    GaitTimer timer;
-    bool walking = true;
-    double velocity_base[6] = {0, 0, 0, 0, 0, 0};
-    std::vector<double> x_reference, x_model_ref;
-    stream_t stream;
     // SMPC_STREAMS=2: the iterations of the two halves of the batch run on two streams, so that workgroups of the matrix-core bound
     // Riccati sweep of one half share the CUs with the VALU bound stage kernels of the other
     static constexpr int MAX_STREAMS = 4;
     stream_t streams[MAX_STREAMS] = {};  // streams[0] == stream
-    stream_t cur{};      // stream of the launches being issued
     int n_streams = 1;
     int * und_lists[MAX_STREAMS] = {nullptr, nullptr, nullptr, nullptr}; // und_lists[0] == buf.und_list
     event_t ev_fork{}, ev_join[MAX_STREAMS] = {};
     double * X_dev = nullptr;
-    double * stage_out = nullptr; // staging for linearised outputs
-    size_t stage_out_bytes = 0;
-    int cold_iters = 0;
     int riccati_nt = xcheck_env("SMPC_RICCATI_NT") ? std::atoi(xcheck_env("SMPC_RICCATI_NT")) : 128; // dense sweep: lanes per instance
     // SMPC_RICCATI=dense selects the model-independent sweep (A/B comparison and cross-check in the tests)
     bool structured_riccati = !(xcheck_env("SMPC_RICCATI") && std::string(xcheck_env("SMPC_RICCATI")) == "dense");
-    std::vector<double> cold_trace; // [n][4] phi0, prim, dual, alpha
-    // profiling
-    bool profiling = false;
     static constexpr int LS_SLOTS = 64; // instance slots of the list-mode (backtracking) launches: 64 x (H+1) blocks when the list is empty
     bool speculative_ls = xcheck_env("SMPC_NO_SPECULATIVE_LS") == nullptr; // tentative full steps (run_iterations)
-    bool early_exit_on_tol = false; // smpc_set_early_exit_on_tol: iterate() stops an instance's iterations once it is converged to TOL
-    bool aux_launches = false; // true during the cold start: every launch uses the auxiliary kernel symbols
     // lane-per-problem stage evaluation (smpc_kino_lane.h) for problems without optional constraint blocks; SMPC_LANE_EVAL=0: the
     // wavefront-per-problem kernels throughout (A/B comparison)
     int lane_slots = 1;
@@ -381,15 +203,12 @@ namespace smpc
     bool lane_stream = !(xcheck_env("SMPC_LANE_STREAM") && std::atoi(xcheck_env("SMPC_LANE_STREAM")) == 0);
     bool stream_order_recorded = false;
     int foot_joint_h[D::NF] = {0}; // (host copy for deriv2_commit_code)
-    double kernel_ms[KID_N] = {0};
-    long kernel_calls[KID_N] = {0};
-    std::vector<std::pair<int, std::pair<event_t, event_t>>> pending_events;
     static constexpr int TRIAL_MINW = SMPC_TRIAL_MINW; // waves per SIMD the trial kernel's register budget allows
     static constexpr int RICCATI_MINW = 2;             // the Riccati sweep is latency bound: 2 waves per SIMD (8 per CU, 19.8 KB LDS each)
     static constexpr double ARMIJO_C1 = 1e-4, REG_INIT = 1e-9, REG_MIN = 1e-10, REG_MAX = 1e9, REG_INC = 10.0, REG_DEC = 1.0 / 3.0, STALL_REL = 1e-9;
 
     KinoEngine(const smpc_robot_model * rm, const HostKinoSettings & ks, const HostMpcSettings & ms_, int batch, double gravity_arg, int device)
-    : ms(ms_)
+    : MpcEngineBase(ms_, batch, device)
     {
       AllocScope ctor_scope; // (a throw below releases what was allocated so far: smpc_alloc_scope.h)
       if (rm->njoints != D::NJ || rm->nfeet != D::NF)
@@ -406,25 +225,21 @@ namespace smpc
         if ((const char *)probe.WJl - (const char *)probe.cval != (std::ptrdiff_t)(KinoScratchEval<D>::LATE_DOUBLES * sizeof(double)))
           throw std::runtime_error("internal: KinoScratch layout is not contiguous across its two parts");
       }
-      device_id = device;
-      set_device(device);
-      stream = stream_create();
-      cur = stream;
+      open_stream();
       streams[0] = stream;
       if (std::getenv("SMPC_STREAMS"))
         n_streams = std::min(std::max(std::atoi(std::getenv("SMPC_STREAMS")), 1), (int)MAX_STREAMS);
       if (n_streams > 1)
       {
-        ev_fork = event_create();
+        ev_fork = side.event();
         for (int i = 1; i < n_streams; i++)
         {
-          streams[i] = stream_create();
-          ev_join[i] = event_create();
+          streams[i] = side.stream();
+          ev_join[i] = side.event();
         }
       }
-      B = batch;
-      H = ms.T;
-      R = H + 1;
+      const int dd[8] = {D::NQ, D::NV, D::NX, D::NDX, D::NU, D::NC, D::NF, H};
+      std::copy(dd, dd + 8, dims);
       // ---- model table ----
       std::vector<DevModel<D>> hm(1);
       DevModel<D> & m = hm[0];
@@ -495,7 +310,7 @@ namespace smpc
       buf.dlams = dalloc(BH * D::NDX);
       buf.foot_ref = dalloc(BH * D::NF * 3);
       buf.ftraj = dalloc((size_t)B * D::NF * 6);
-      buf.vbase = dalloc((size_t)B * 6);
+      buf.vbase = vbase_dev = dalloc((size_t)B * 6);
       buf.vref = dalloc(BR * 6);
       buf.lq = dalloc(BH * D::LQ_STRIDE);
       buf.gains = dalloc(BH * (size_t)std::max((int)D::G_STRIDE, (int)GainsK<D>::STRIDE));
@@ -617,31 +432,20 @@ namespace smpc
       for (double * p : {buf.CN, buf.vN, buf.vN_e, buf.vN_b, buf.dvN, buf.dcm_ref, buf.es, buf.es_e, buf.es_b, buf.des, buf.ek, buf.ls, buf.ls_e, buf.ls_b, buf.dls, buf.lk})
         dev_free(p);
       for (double * p : {buf.xs_b, buf.us_b, buf.vs_b, buf.lams_b, buf.xs, buf.us, buf.vs, buf.lams, buf.vs_e, buf.lams_e, buf.dxs, buf.dus, buf.dvs, buf.dlams, buf.foot_ref, buf.ftraj, buf.vbase, buf.vref, buf.lq,
-                         buf.gains, buf.ev, buf.QN, buf.qN, buf.parts0, buf.partsT, buf.scal, buf.xdotT, buf.xdot01, X_dev, stage_out})
+                         buf.gains, buf.ev, buf.QN, buf.qN, buf.parts0, buf.partsT, buf.scal, buf.xdotT, buf.xdot01, X_dev})
         dev_free(p);
       dev_free(buf.ls_sel);
       dev_free(buf.und_list);
       dev_free(buf.evd);
       dev_free(buf.ev_order);
-      if (ev_handoff_valid)
-        event_destroy(ev_handoff);
       dev_free(sim_a);
       dev_free(sim_lam);
       dev_free(sim_mask);
       for (int i = 1; i < n_streams; i++)
-      {
         dev_free(und_lists[i]);
-        stream_destroy(streams[i]);
-        event_destroy(ev_join[i]);
-      }
-      if (n_streams > 1)
-        event_destroy(ev_fork);
       dev_free(buf.stages);
       dev_free(buf.model);
-      stream_destroy(stream);
     }
-    KinoEngine(const KinoEngine &) = delete;
-    KinoEngine & operator=(const KinoEngine &) = delete;
 
     SolverArgs<D> solver_args(const Buffers<D> & b, int j0 = 0, int nj = 0) const
     {
@@ -657,43 +461,6 @@ namespace smpc
       a.reg_dec = REG_DEC;
       a.stop_tol = early_exit_on_tol ? ms.TOL : -1.0;
       return a;
-    }
-
-    // aux: auxiliary launch (cold start on one instance, list-mode launch of the backtracking path): same code under a
-    // second kernel symbol, so that profiler averages of the main symbol are those of full-batch launches
-    template <class Args, void (*Body)(const Args &, int), int NT, int MINW = 1>
-    void timed_launch(int kid, int grid, const Args & a, bool aux = false)
-    {
-      set_device(device_id);
-      aux = aux || aux_launches;
-      event_t e0{}, e1{};
-      if (profiling)
-      {
-        e0 = event_create();
-        e1 = event_create();
-        event_record(e0, cur);
-      }
-      if (aux)
-        launch<Args, Body, NT, MINW, 1>(grid, cur, a);
-      else
-        launch<Args, Body, NT, MINW, 0>(grid, cur, a);
-      if (profiling)
-      {
-        event_record(e1, cur);
-        pending_events.push_back({kid, {e0, e1}});
-      }
-      kernel_calls[kid]++;
-    }
-    void collect_profile()
-    {
-      stream_sync(stream);
-      for (auto & pe : pending_events)
-      {
-        kernel_ms[pe.first] += event_elapsed_ms(pe.second.first, pe.second.second);
-        event_destroy(pe.second.first);
-        event_destroy(pe.second.second);
-      }
-      pending_events.clear();
     }
 
     StageKernelArgs<D> stage_args(const Buffers<D> & b, int slots = 0) const
@@ -1046,7 +813,7 @@ namespace smpc
       }
     }
 
-    void generate_cycle_horizon(const unsigned char * cs, int n)
+    void generate_cycle_horizon(const unsigned char * cs, int n) override
     {
       if (n <= 0)
         throw std::runtime_error("contact sequence must not be empty");
@@ -1073,41 +840,8 @@ namespace smpc
         cycle.push_back(s);
       }
     }
-    // velocity commands live on the device, one per instance; the reference's single velocity_base_ is a broadcast
-    void upload_velocity(const double * V, bool broadcast)
-    {
-      set_device(device_id);
-      std::vector<double> h((size_t)B * 6);
-      for (int b = 0; b < B; b++)
-        for (int i = 0; i < 6; i++)
-          h[(size_t)b * 6 + i] = broadcast ? V[i] : V[(size_t)b * 6 + i];
-      h2d(buf.vbase, h.data(), h.size() * sizeof(double), stream);
-      stream_sync(stream);
-    }
-    void switch_to_walk(const double * v6)
-    {
-      walking = true;
-      for (int i = 0; i < 6; i++)
-        velocity_base[i] = v6[i];
-      upload_velocity(v6, true);
-    }
-    void switch_to_stand()
-    {
-      walking = false;
-      for (int i = 0; i < 6; i++)
-        velocity_base[i] = 0.0;
-      upload_velocity(velocity_base, true);
-    }
-    // one velocity command per instance, V: [B][6] (the walking state is unchanged, like assigning MPC::velocity_base_)
-    void set_velocity_base_batched(const double * V)
-    {
-      for (int i = 0; i < 6; i++)
-        velocity_base[i] = V[i];
-      upload_velocity(V, false);
-    }
-
     // One control step for the whole batch; Xd: device pointer [B][NX]
-    void iterate_device(const double * Xd)
+    void iterate_device(const double * Xd) override
     {
       ref_rot.reset(); // (every control step rewrites every stage's reference pose with the identity rotation: src/mpc.cpp:303-309)
       if (cycle.empty())
@@ -1225,26 +959,8 @@ namespace smpc
     // ---- per-stage references of the horizon: the OCPHandler setters / getters (reference src/kinodynamics.cpp:154-306,
     //      src/ocp-handler.cpp:58-81), broadcast over the batch.  The next iterate() overwrites the foot references of
     //      every stage and the state target of stage H-1, exactly like MPC::updateStepTrackerReferences does. ----
-    void check_stage(int t) const
-    {
-      if (t < 0 || t >= H)
-        throw std::runtime_error("Stage index exceeds stage vector size");
-    }
-    void fill_strided(double * base, size_t stride, int count, const double * v, int n)
-    {
-      set_device(device_id);
-      FillStridedArgs fa;
-      fa.base = base;
-      fa.stride = stride;
-      fa.count = count;
-      fa.n = n;
-      for (int i = 0; i < n; i++)
-        fa.v[i] = v[i];
-      launch<FillStridedArgs, fill_strided_body, 64>((count + 63) / 64, stream, fa);
-      stream_sync(stream);
-    }
     // what: 0 = control target (nu), 1 = state target (nx)
-    void set_stage_reference(int t, int what, const double * v, int n)
+    void set_stage_reference(int t, int what, const double * v, int n) override
     {
       check_stage(t);
       if (what == 0)
@@ -1263,7 +979,7 @@ namespace smpc
       else
         throw std::runtime_error("unknown stage reference");
     }
-    void get_stage_reference(int t, int what, double * v, int n)
+    void get_stage_reference(int t, int what, double * v, int n) override
     {
       check_stage(t);
       if (what == 0 && n == D::NU)
@@ -1276,37 +992,21 @@ namespace smpc
       else
         throw std::runtime_error("unknown stage reference or wrong size");
     }
-    void set_reference_pose(int t, int foot, const double * p3)
+    void set_reference_pose(int t, int foot, const double * p3) override
     {
       check_stage(t);
-      if (foot < 0 || foot >= D::NF)
-        throw std::runtime_error("unknown end effector");
+      check_foot(foot);
       ref_rot.set(t, foot, nullptr); // (a translation: identity rotation)
       fill_strided(buf.foot_ref + ((size_t)t * D::NF + foot) * 3, (size_t)H * D::NF * 3, B, p3, 3);
     }
-    void get_reference_pose(int t, int foot, int inst, double * p3)
+    void get_reference_pose(int t, int foot, int inst, double * p3) override
     {
       check_stage(t);
       if (foot < 0 || foot >= D::NF || inst < 0 || inst >= B)
         throw std::runtime_error("unknown end effector or instance");
       get_linear(buf.foot_ref + (((size_t)inst * H + t) * D::NF + foot) * 3, 3, p3);
     }
-    RefRotations ref_rot; // rotations of the foot reference placements: API state (smpc_model.h)
-    void set_reference_rotation(int t, int foot, const double * R9)
-    {
-      check_stage(t);
-      if (foot < 0 || foot >= D::NF)
-        throw std::runtime_error("unknown end effector");
-      ref_rot.set(t, foot, R9);
-    }
-    void get_reference_rotation(int t, int foot, double * R9)
-    {
-      check_stage(t);
-      if (foot < 0 || foot >= D::NF)
-        throw std::runtime_error("unknown end effector");
-      ref_rot.get(t, foot, R9);
-    }
-    unsigned contact_mask(int t) const
+    unsigned contact_mask(int t) const override
     {
       check_stage(t);
       return horizon[t].mask;
@@ -1314,7 +1014,7 @@ namespace smpc
 
     // Everything a later iterate() depends on: iterate, multipliers, swing trajectories, references, velocity commands, gait
     // bookkeeping.  Not included: the feedback gains and the LQ knots of the last solve (recomputed by the next iterate).
-    size_t state_io(StateIO & io)
+    size_t state_io(StateIO & io) override
     {
       set_device(device_id);
       stream_sync(stream);
@@ -1356,7 +1056,7 @@ namespace smpc
       return io.pos;
     }
     // xdot of every stage at the iterate of the last solve, out [B][H][2 NV] (device): one launch on the handle's stream (smpc_xdot.h)
-    void state_derivatives(double * out)
+    void state_derivatives(double * out) override
     {
       set_device(device_id);
       XdotArgs<Buffers<D>> a;
@@ -1370,7 +1070,7 @@ namespace smpc
       else
         launch<XdotArgs<Buffers<D>>, xdot_all_body<D, Buffers<D>, XD_KINO_WAVE>, 64>(xdot_grid(XD_KINO_WAVE, B, H), stream, a);
     }
-    void iterate_host(const double * X)
+    void iterate_host(const double * X) override
     {
       set_device(device_id);
       h2d(X_dev, X, (size_t)B * D::NX * sizeof(double), stream);
@@ -1378,22 +1078,17 @@ namespace smpc
       stream_sync(stream);
     }
     // the same without the final synchronisation: X must stay valid until sync() (one host thread can then keep several devices busy)
-    void iterate_host_async(const double * X)
+    void iterate_host_async(const double * X) override
     {
       set_device(device_id);
       h2d(X_dev, X, (size_t)B * D::NX * sizeof(double), stream);
       iterate_device(X_dev);
     }
-    void sync()
-    {
-      set_device(device_id);
-      stream_sync(stream);
-    }
     // What a controller consumes of a control step -- xs[1], us[0], K_0 -- of every instance as rows [x1 (NX) | u0 (NU) | K0 (NU x NDX)] of
     // `out`, `row_doubles` apart (the small return set of the sharded batch, gathered into ONE host buffer -- pinned by the
     // caller for full PCIe rate -- that several handles, one per device, fill side by side).  Asynchronous: sync() completes it.
     static constexpr int GATHER_ROW = D::NX + D::NU + D::NU * D::NDX;
-    void gather_outputs_async(double * out, size_t row_doubles)
+    void gather_outputs_async(double * out, size_t row_doubles) override
     {
       set_device(device_id);
       if (row_doubles < (size_t)GATHER_ROW)
@@ -1420,7 +1115,7 @@ namespace smpc
     }
     // the same rows packed into a DEVICE buffer (one kernel), for a caller that moves them itself: a collective towards the rank that
     // owns the controllers, or one copy into pinned memory from a side stream.  Asynchronous on the engine's stream.
-    void gather_outputs_device(double * out_dev, size_t row_doubles)
+    void gather_outputs_device(double * out_dev, size_t row_doubles) override
     {
       set_device(device_id);
       if (row_doubles < (size_t)GATHER_ROW)
@@ -1440,15 +1135,17 @@ namespace smpc
     // ... and into a buffer of ANOTHER device of the node: packed here, then one peer copy over xGMI on this engine's stream (the form
     // SURVEY 8e lists for a single process that drives all devices: every device's rows land in one buffer on the device -- or next to the
     // host thread -- that runs the controllers).  dst: [batch][GATHER_ROW] doubles, contiguous.
-    void gather_outputs_peer(double * dst, int dst_device)
+    void gather_outputs_peer(double * dst, int dst_device) override
     {
+      if (dst_device < 0 || dst_device >= device_count())
+        throw InvalidCall("destination device out of range");
       const size_t bytes = (size_t)B * GATHER_ROW * sizeof(double);
       double * dev = staging(bytes);
       gather_outputs_device(dev, GATHER_ROW);
       d2peer(dst, dst_device, dev, device_id, bytes, stream);
     }
     // xs[t] of every instance -> dense device buffer [B][NX], asynchronous on the engine's stream
-    void gather_x_device(int t, double * out_dev)
+    void gather_x_device(int t, double * out_dev) override
     {
       if (t < 0 || t > H)
         throw std::runtime_error("Stage index exceeds stage vector size");
@@ -1461,7 +1158,7 @@ namespace smpc
     }
 
     // u = u_interp - K_0 (x_interp (-) x_meas) at `delay` after the last solve, for measured states X [B][NX] (host)
-    void riccati_feedback(double delay, const double * X, double * u_out)
+    void riccati_feedback(double delay, const double * X, double * u_out) override
     {
       if (!structured_riccati)
         throw std::runtime_error("riccati_feedback needs the structured Riccati sweep (unset SMPC_RICCATI)");
@@ -1500,7 +1197,7 @@ namespace smpc
     }
 
     // state feedback front-end on measured states X [B][NX] (host): host outputs, any may be null
-    void update_internal_data(const double * X, double * feet, double * com, double * hg, double * cstate)
+    void update_internal_data(const double * X, double * feet, double * com, double * hg, double * cstate) override
     {
       const size_t nf = (size_t)B * D::NF * 3, nc = (size_t)B * 3, nh = (size_t)B * 6, ns = (size_t)B * 9;
       double * st = staging((nf + nc + nh + ns) * sizeof(double));
@@ -1527,7 +1224,7 @@ namespace smpc
     // constrained forward dynamics of the full-dynamics model for n states (host buffers; iters / kernel_ms may be null)
     void full_forward_dynamics(
       int n, const double * X, const double * tau, const unsigned * mask, const double * Kp, const double * Kd,
-      double prox_accuracy, double prox_mu, int prox_max_iter, double * a, double * lam, int * iters, double * kernel_ms)
+      double prox_accuracy, double prox_mu, int prox_max_iter, double * a, double * lam, int * iters, double * kernel_ms) override
     {
       if (n < 1)
         throw std::runtime_error("full_forward_dynamics: n must be positive");
@@ -1571,7 +1268,7 @@ namespace smpc
     // One step of a simulated batch with states and torques resident in HBM (what the reference's examples do with a physics engine
     // between two controller ticks): constrained forward dynamics of the feet in `mask` (Baumgarte gains Kp, Kd; proximal settings of
     // record), then semi-implicit Euler over dt, X updated in place.  Asynchronous on this engine's stream.
-    void sim_step_device(double * X_dev, const double * tau_dev, unsigned mask, const double * Kp, const double * Kd, double dt)
+    void sim_step_device(double * X_dev, const double * tau_dev, unsigned mask, const double * Kp, const double * Kd, double dt) override
     {
       set_device(device_id);
       constexpr int NV = D::NV, NCM = 3 * D::NF;
@@ -1612,25 +1309,11 @@ namespace smpc
       sa.dt = dt;
       launch<SimStepArgs<D>, sim_integrate_body<D>, 64>(B, stream, sa);
     }
-    // work issued on `other` from now on starts after what this engine's stream holds now
-    void wait_stream(stream_t other)
-    {
-      set_device(device_id);
-      if (!ev_handoff_valid)
-      {
-        ev_handoff = event_create();
-        ev_handoff_valid = true;
-      }
-      event_record(ev_handoff, stream);
-      stream_wait_event(other, ev_handoff);
-    }
-    event_t ev_handoff{};
-    bool ev_handoff_valid = false;
     double *sim_a = nullptr, *sim_lam = nullptr;
     unsigned * sim_mask = nullptr;
     unsigned sim_mask_value = ~0u;
     // the same into device buffers (the inverse-dynamics engine's target buffers), asynchronous on this engine's stream
-    void interpolate_device(double delay, int knots, double * x_dev, double * acc_dev, double * f_dev)
+    void interpolate_device(double delay, int knots, double * x_dev, double * acc_dev, double * f_dev) override
     {
       if (knots < 2 || knots > H + 1)
         throw std::runtime_error("interpolate: knots must be in [2, horizon + 1]");
@@ -1649,7 +1332,7 @@ namespace smpc
       launch<InterpArgs<D>, interp_body<D>, 64>(B, stream, ia);
     }
     // interpolated whole-body targets at `delay` after the last solve; host outputs, any may be null
-    void interpolate(double delay, int knots, double * x_out, double * acc_out, double * f_out)
+    void interpolate(double delay, int knots, double * x_out, double * acc_out, double * f_out) override
     {
       if (knots < 2 || knots > H + 1)
         throw std::runtime_error("interpolate: knots must be in [2, horizon + 1]");
@@ -1676,36 +1359,6 @@ namespace smpc
       stream_sync(stream);
     }
 
-    double * staging(size_t bytes)
-    {
-      set_device(device_id);
-      if (bytes > stage_out_bytes)
-      {
-        dev_free(stage_out);
-        stage_out = (double *)dev_alloc(bytes);
-        stage_out_bytes = bytes;
-      }
-      return stage_out;
-    }
-    // ring array [B][R][n] -> host linear [B][count][n] for t = 0..count-1
-    void get_ring(const double * src, int n, int count, double * out)
-    {
-      set_device(device_id);
-      stream_sync(stream);
-      std::vector<double> tmp((size_t)B * R * n);
-      d2h(tmp.data(), src, tmp.size() * sizeof(double), stream);
-      stream_sync(stream);
-      for (int b = 0; b < B; b++)
-        for (int t = 0; t < count; t++)
-          std::memcpy(out + ((size_t)b * count + t) * n, tmp.data() + ((size_t)b * R + ring_slot(head, t, R)) * n, n * sizeof(double));
-    }
-    void get_linear(const double * src, size_t n, double * out)
-    {
-      set_device(device_id);
-      stream_sync(stream);
-      d2h(out, src, n * sizeof(double), stream);
-      stream_sync(stream);
-    }
     // K_t of every stage [B][H][NU][NDX] (strided out of the gains block) or only K_0 [B][NU][NDX]
     void get_K(double * out, bool all)
     {
@@ -1734,6 +1387,82 @@ namespace smpc
           for (int i = 0; i < D::NU; i++)
             std::memcpy(out + (((size_t)b * nt + t) * D::NU + i) * D::NDX, row.data() + (size_t)i * (D::NDX + 1), D::NDX * sizeof(double));
         }
+    }
+    void get_output(Output what, double * out) override
+    {
+      switch (what)
+      {
+      case OUT_XS:
+        return get_ring(buf.xs, D::NX, H + 1, out);
+      case OUT_US:
+        return get_ring(buf.us, D::NU, H, out);
+      case OUT_K0:
+        return get_K(out, false);
+      case OUT_KS:
+        return get_K(out, true);
+      case OUT_VS:
+        return get_ring(buf.vs, D::NC, H, out);
+      case OUT_LAMS:
+        return get_lams(buf.lams, D::NDX, out);
+      case OUT_XDOT01:
+        return get_linear(buf.xdot01, (size_t)B * 4 * D::NV, out);
+      case OUT_FOOT_REFS:
+        return get_linear(buf.foot_ref, (size_t)B * H * D::NF * 3, out);
+      case OUT_INFO:
+        return get_linear(buf.scal, (size_t)B * SC_N, out);
+      default:
+        throw InvalidCall("smpc_get_contact_forces needs a full-dynamics handle (the other problems carry the forces in us)");
+      }
+    }
+    // multipliers of the optional rows: 0 = friction cones [B][H][2 NF], 1 = land rows [B][H][NF]
+    void get_extra_multipliers(int which, double * out) override
+    {
+      double * src = which == 0 ? buf.es : buf.ls;
+      if (!src)
+        throw InvalidCall("the problem has no such rows");
+      get_ring(src, which == 0 ? 2 * D::NF : D::NF, H, out);
+    }
+    int lq_size() const override { return kino_lq_size<D>(); }
+    void debug_lq(int inst, int t, double * out) override
+    {
+      if (inst < 0 || inst >= B || t < 0 || t >= H)
+        throw InvalidCall("Stage index exceeds stage vector size");
+      // the device keeps [Q S; S^T R] as accumulator-layout tiles (Dims::O_T); returned in the documented row-major order
+      // A | B | Q | S | R | C | q | r | f | d | lx | lu | lpd | vpd
+      std::vector<double> raw(D::LQ_STRIDE);
+      get_linear(buf.lq + ((size_t)inst * H + t) * D::LQ_STRIDE, D::LQ_STRIDE, raw.data());
+      constexpr int n = D::NDX, m = D::NU;
+      double * o = out;
+      std::copy(raw.begin() + D::O_A, raw.begin() + D::O_T, o); // A | B
+      o += D::O_T - D::O_A;
+      for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++)
+          *o++ = raw[D::q_off(i, j)];
+      for (int i = 0; i < n; i++)
+        for (int j = 0; j < m; j++)
+          *o++ = raw[D::s_off(i, j)];
+      for (int i = 0; i < m; i++)
+        for (int j = 0; j < m; j++)
+          *o++ = raw[D::r_off(i, j)];
+      std::copy(raw.begin() + D::O_C, raw.begin() + D::O_vpd + D::NC, o);
+    }
+    void debug_steps(double * dxs, double * dus) override
+    {
+      get_linear(buf.dxs, (size_t)B * (H + 1) * D::NDX, dxs);
+      get_linear(buf.dus, (size_t)B * H * D::NU, dus);
+    }
+    void debug_terminal(int inst, double * QN, double * qN) override
+    {
+      if (inst < 0 || inst >= B)
+        throw InvalidCall("instance index out of range");
+      get_linear(buf.QN + (size_t)inst * D::NDX * D::NDX, D::NDX * D::NDX, QN);
+      get_linear(buf.qN + (size_t)inst * D::NDX, D::NDX, qN);
+    }
+    void phase_cycles(double * out64) override
+    {
+      if (!buf.dbg)
+        throw InvalidCall("phase timers are off (set SMPC_PHASE_PROFILE=1 before smpc_create)");
+      get_linear(buf.dbg, 64, out64);
     }
   };
 } // namespace smpc

@@ -22,61 +22,8 @@ namespace smpc
     int terminal_constraint = 0; // createProblem(..., terminal_constraint)
   };
 
-  // what the C ABI needs from a full-dynamics engine of any robot shape
-  struct FullEngineBase
-  {
-    int B = 0, H = 0, R = 0, head = 0;
-    int device_id = 0;
-    int dims[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // nq nv nx ndx nu nc nf H
-    int force_size = 3;
-    GaitTimer timer;
-    stream_t stream;
-    bool profiling = false;
-    double kernel_ms[KID_N] = {0};
-    long kernel_calls[KID_N] = {0};
-    int cold_iters = 0;
-    std::vector<double> cold_trace;
-    std::vector<double> x_reference;
-    virtual void set_early_exit(bool on) = 0;
-    virtual ~FullEngineBase() {}
-    virtual void generate_cycle_horizon(const unsigned char * cs, int n) = 0;
-    virtual void switch_to_walk(const double * v6) = 0;
-    virtual void switch_to_stand() = 0;
-    virtual void set_velocity_base_batched(const double * V) = 0;
-    virtual void iterate_host(const double * X) = 0;
-    virtual void iterate_device(const double * Xd) = 0;
-    virtual void sync() = 0;
-    virtual void gather_x_device(int t, double * out_dev) = 0;
-    virtual void get(int what, double * out) = 0; // 0 xs 1 us 2 K0 3 Ks 4 vs 5 lams 6 xdot01 7 foot refs 8 info 9 contact forces
-    virtual void set_stage_reference(int t, int what, const double * v, int n) = 0;
-    virtual void get_stage_reference(int t, int what, double * v, int n) = 0;
-    virtual void set_reference_pose(int t, int foot, const double * p3) = 0;
-    virtual void get_reference_pose(int t, int foot, int inst, double * p3) = 0;
-    virtual void set_reference_rotation(int t, int foot, const double * R9) = 0;
-    virtual void get_reference_rotation(int t, int foot, double * R9) = 0;
-    virtual unsigned contact_mask(int t) const = 0;
-    virtual void update_internal_data(const double * X, double * feet, double * com, double * hg, double * cstate) = 0;
-    virtual void full_forward_dynamics(int n, const double * X, const double * tau, const unsigned * mask, const double * Kp, const double * Kd,
-                                       double prox_accuracy, double prox_mu, int prox_max_iter, double * a, double * lam, int * iters, double * kernel_ms) = 0;
-    virtual size_t state_io(StateIO & io) = 0;
-    virtual void collect_profile() = 0;
-    virtual int lq_size() const = 0;
-    virtual void debug_lq(int inst, int t, double * out) = 0;
-    virtual void debug_steps(double * dxs, double * dus) = 0;
-    virtual void debug_terminal(int inst, double * QN, double * qN) = 0;
-    virtual bool phase_cycles(double * out64) = 0;
-    virtual void interpolate(double delay, int knots, double * x_out, double * acc_out, double * f_out) = 0;
-    // device-resident forms (nothing crosses the host between two MPC steps): the interpolated targets written into the
-    // inverse-dynamics engine's device buffers, the simulated robot stepped in place, ordering with another stream
-    virtual void interpolate_device(double delay, int knots, double * x_dev, double * acc_dev, double * f_dev) = 0;
-    virtual void sim_step_device(double * X_dev, const double * tau_dev, unsigned mask, const double * Kp, const double * Kd, double dt) = 0;
-    virtual void wait_stream(stream_t other) = 0;
-    virtual void riccati_feedback(double delay, const double * X, double * u_out) = 0;
-    virtual void state_derivatives(double * out) = 0; // xdot of every stage at the last solve's iterate, [B][H][2 NV] (device, handle's stream)
-  };
-
   template <class D>
-  class FullEngine : public FullEngineBase
+  class FullEngine : public MpcEngineBase
   {
   public:
     Buffers<D> buf;
@@ -89,25 +36,14 @@ namespace smpc
     // before; the quadruped (B = 4096): 70.5 k -> 71.3 k.  Kept off.  Instances are independent: bit-identical results (tests).
     static constexpr int MAX_PARTS = 4;
     int n_parts = 1;
-    stream_t cur{};                      // the stream the launches of the moment go to
     stream_t part_stream[MAX_PARTS] = {}; // [0] = stream
     event_t ev_fork{}, ev_join[MAX_PARTS] = {};
     int * und_part[MAX_PARTS] = {nullptr, nullptr, nullptr, nullptr};
-    HostMpcSettings ms;
     std::vector<StageShared<D>> horizon, cycle;
     StageShared<D> standing;
-    bool walking = true;
-    double velocity_base[6] = {0, 0, 0, 0, 0, 0};
-    std::vector<double> x_model_ref;
     double * X_dev = nullptr;
-    double * stage_out = nullptr;
-    size_t stage_out_bytes = 0;
     bool valu_riccati = xcheck_env("SMPC_RICCATI") && std::string(xcheck_env("SMPC_RICCATI")) == "valu";
     bool speculative_ls = xcheck_env("SMPC_NO_SPECULATIVE_LS") == nullptr;
-    bool early_exit_on_tol = false; // smpc_set_early_exit_on_tol
-    void set_early_exit(bool on) override { early_exit_on_tol = on; }
-    bool aux_launches = false;
-    std::vector<std::pair<int, std::pair<event_t, event_t>>> pending_events;
     static constexpr int LS_SLOTS = 64;
 #ifndef SMPC_FDYN_DERIV_MINW
 #define SMPC_FDYN_DERIV_MINW 1
@@ -118,7 +54,7 @@ namespace smpc
     double ref_foot_pos[D::NF][3];
 
     FullEngine(const smpc_robot_model * rm, const HostFullSettings & fs, const HostMpcSettings & ms_, int batch, double gravity_arg, int device)
-    : ms(ms_)
+    : MpcEngineBase(ms_, batch, device)
     {
       AllocScope ctor_scope; // (a throw below releases what was allocated so far: smpc_alloc_scope.h)
       if (rm->njoints != D::NJ || rm->nfeet != D::NF)
@@ -139,14 +75,8 @@ namespace smpc
         throw std::runtime_error("internal: land_cstr needs the instantiation with land rows");
       if (fs.force_cone && D::NCONE1 == 0)
         throw std::runtime_error("internal: force_cone needs the instantiation with cone rows");
-      device_id = device;
-      set_device(device);
-      stream = stream_create();
-      cur = stream;
+      open_stream();
       part_stream[0] = stream;
-      B = batch;
-      H = ms.T;
-      R = H + 1;
       force_size = D::FS;
       const int dd[8] = {D::NQ, D::NV, D::NX, D::NDX, D::NU, D::NC, D::NF, H};
       std::copy(dd, dd + 8, dims);
@@ -236,7 +166,7 @@ namespace smpc
       buf.dlams = dalloc(BH * D::NDX);
       buf.foot_ref = dalloc(BH * D::NF * 3);
       buf.ftraj = dalloc((size_t)B * D::NF * 6);
-      buf.vbase = dalloc((size_t)B * 6);
+      buf.vbase = vbase_dev = dalloc((size_t)B * 6);
       buf.vref = dalloc(BR * 6);
       buf.lq = dalloc(BH * D::LQ_STRIDE);
       buf.gains = dalloc(BH * (size_t)D::G_STRIDE);
@@ -269,11 +199,11 @@ namespace smpc
         }
         if (n_parts > 1)
         {
-          ev_fork = event_create();
+          ev_fork = side.event();
           for (int i = 1; i < n_parts; i++)
           {
-            part_stream[i] = stream_create();
-            ev_join[i] = event_create();
+            part_stream[i] = side.stream();
+            ev_join[i] = side.event();
           }
           for (int i = 0; i < n_parts; i++)
             und_part[i] = (int *)dev_alloc((size_t)(B + 1) * sizeof(int));
@@ -309,32 +239,18 @@ namespace smpc
         dev_free(p);
       for (double * p : {buf.xs_b, buf.us_b, buf.vs_b, buf.lams_b, buf.xs, buf.us, buf.vs, buf.lams, buf.vs_e, buf.lams_e, buf.dxs, buf.dus, buf.dvs, buf.dlams, buf.foot_ref,
                          buf.ftraj, buf.vbase, buf.vref, buf.lq, buf.gains, buf.QN, buf.qN, buf.parts0, buf.partsT, buf.scal, buf.xdotT, buf.xdot01, buf.forces,
-                         buf.forcesT, X_dev, stage_out, deriv_wide})
+                         buf.forcesT, X_dev, deriv_wide})
         dev_free(p);
       dev_free(buf.ls_sel);
       dev_free(buf.und_list);
       for (int i = 0; i < MAX_PARTS; i++)
         dev_free(und_part[i]);
-      if (n_parts > 1)
-      {
-        event_destroy(ev_fork);
-        for (int i = 1; i < n_parts; i++)
-        {
-          event_destroy(ev_join[i]);
-          stream_destroy(part_stream[i]);
-        }
-      }
       dev_free(buf.stages);
       dev_free(buf.model);
       dev_free(sim_a);
       dev_free(sim_lam);
       dev_free(sim_mask);
-      if (ev_handoff_valid)
-        event_destroy(ev_handoff);
-      stream_destroy(stream);
     }
-    FullEngine(const FullEngine &) = delete;
-    FullEngine & operator=(const FullEngine &) = delete;
 
     SolverArgs<D> solver_args(const Buffers<D> & b, int j0 = 0, int nj = 0) const
     {
@@ -350,40 +266,6 @@ namespace smpc
       a.reg_dec = REG_DEC;
       a.stop_tol = early_exit_on_tol ? ms.TOL : -1.0;
       return a;
-    }
-    template <class Args, void (*Body)(const Args &, int), int NT, int MINW = 1>
-    void timed_launch(int kid, int grid, const Args & a, bool aux = false)
-    {
-      set_device(device_id);
-      aux = aux || aux_launches;
-      event_t e0{}, e1{};
-      if (profiling)
-      {
-        e0 = event_create();
-        e1 = event_create();
-        event_record(e0, cur);
-      }
-      if (aux)
-        launch<Args, Body, NT, MINW, 1>(grid, cur, a);
-      else
-        launch<Args, Body, NT, MINW, 0>(grid, cur, a);
-      if (profiling)
-      {
-        event_record(e1, cur);
-        pending_events.push_back({kid, {e0, e1}});
-      }
-      kernel_calls[kid]++;
-    }
-    void collect_profile() override
-    {
-      stream_sync(stream);
-      for (auto & pe : pending_events)
-      {
-        kernel_ms[pe.first] += event_elapsed_ms(pe.second.first, pe.second.second);
-        event_destroy(pe.second.first);
-        event_destroy(pe.second.second);
-      }
-      pending_events.clear();
     }
     StageKernelArgs<D> stage_args(const Buffers<D> & b, int slots = 0) const
     {
@@ -645,37 +527,6 @@ namespace smpc
         cycle.push_back(s);
       }
     }
-    void upload_velocity(const double * V, bool broadcast)
-    {
-      set_device(device_id);
-      std::vector<double> hh((size_t)B * 6);
-      for (int b = 0; b < B; b++)
-        for (int i = 0; i < 6; i++)
-          hh[(size_t)b * 6 + i] = broadcast ? V[i] : V[(size_t)b * 6 + i];
-      h2d(buf.vbase, hh.data(), hh.size() * sizeof(double), stream);
-      stream_sync(stream);
-    }
-    void switch_to_walk(const double * v6) override
-    {
-      walking = true;
-      for (int i = 0; i < 6; i++)
-        velocity_base[i] = v6[i];
-      upload_velocity(v6, true);
-    }
-    void switch_to_stand() override
-    {
-      walking = false;
-      for (int i = 0; i < 6; i++)
-        velocity_base[i] = 0.0;
-      upload_velocity(velocity_base, true);
-    }
-    void set_velocity_base_batched(const double * V) override
-    {
-      for (int i = 0; i < 6; i++)
-        velocity_base[i] = V[i];
-      upload_velocity(V, false);
-    }
-
     void iterate_device(const double * Xd) override
     {
       ref_rot.reset(); // (every control step rewrites every stage's reference pose with the identity rotation: src/mpc.cpp:303-309)
@@ -781,11 +632,6 @@ namespace smpc
       a.out = out;
       launch<XdotArgs<Buffers<D>>, xdot_all_body<D, Buffers<D>, XD_FULL>, 64>(xdot_grid(XD_FULL, B, H), stream, a);
     }
-    void sync() override
-    {
-      set_device(device_id);
-      stream_sync(stream);
-    }
     void gather_x_device(int t, double * out_dev) override
     {
       if (t < 0 || t > H)
@@ -796,24 +642,6 @@ namespace smpc
       ga.t = t;
       ga.out = out_dev;
       launch<GatherArgs<D>, gather_x_body<D>, 256>((int)(((size_t)B * D::NX + 255) / 256), stream, ga);
-    }
-    void check_stage(int t) const
-    {
-      if (t < 0 || t >= H)
-        throw std::runtime_error("Stage index exceeds stage vector size");
-    }
-    void fill_strided(double * base, size_t stride, int count, const double * v, int n)
-    {
-      set_device(device_id);
-      FillStridedArgs fa;
-      fa.base = base;
-      fa.stride = stride;
-      fa.count = count;
-      fa.n = n;
-      for (int i = 0; i < n; i++)
-        fa.v[i] = v[i];
-      launch<FillStridedArgs, fill_strided_body, 64>((count + 63) / 64, stream, fa);
-      stream_sync(stream);
     }
     // what: 0 = control target (nu), 1 = state target (nx), 2 = contact-force references (force_size * nfeet)
     void set_stage_reference(int t, int what, const double * v, int n) override
@@ -863,8 +691,7 @@ namespace smpc
     void set_reference_pose(int t, int foot, const double * p3) override
     {
       check_stage(t);
-      if (foot < 0 || foot >= D::NF)
-        throw std::runtime_error("unknown end effector");
+      check_foot(foot);
       ref_rot.set(t, foot, nullptr); // (a translation: identity rotation)
       fill_strided(buf.foot_ref + ((size_t)t * D::NF + foot) * 3, (size_t)H * D::NF * 3, B, p3, 3);
     }
@@ -874,21 +701,6 @@ namespace smpc
       if (foot < 0 || foot >= D::NF || inst < 0 || inst >= B)
         throw std::runtime_error("unknown end effector or instance");
       get_linear(buf.foot_ref + (((size_t)inst * H + t) * D::NF + foot) * 3, 3, p3);
-    }
-    RefRotations ref_rot; // rotations of the foot reference placements: API state (smpc_model.h)
-    void set_reference_rotation(int t, int foot, const double * R9) override
-    {
-      check_stage(t);
-      if (foot < 0 || foot >= D::NF)
-        throw std::runtime_error("unknown end effector");
-      ref_rot.set(t, foot, R9);
-    }
-    void get_reference_rotation(int t, int foot, double * R9) override
-    {
-      check_stage(t);
-      if (foot < 0 || foot >= D::NF)
-        throw std::runtime_error("unknown end effector");
-      ref_rot.get(t, foot, R9);
     }
     unsigned contact_mask(int t) const override
     {
@@ -1005,35 +817,6 @@ namespace smpc
         stream_sync(stream);
       }
     }
-    double * staging(size_t bytes)
-    {
-      set_device(device_id);
-      if (bytes > stage_out_bytes)
-      {
-        dev_free(stage_out);
-        stage_out = (double *)dev_alloc(bytes);
-        stage_out_bytes = bytes;
-      }
-      return stage_out;
-    }
-    void get_ring(const double * src, int n, int count, double * out)
-    {
-      set_device(device_id);
-      stream_sync(stream);
-      std::vector<double> tmp((size_t)B * R * n);
-      d2h(tmp.data(), src, tmp.size() * sizeof(double), stream);
-      stream_sync(stream);
-      for (int b = 0; b < B; b++)
-        for (int t = 0; t < count; t++)
-          std::memcpy(out + ((size_t)b * count + t) * n, tmp.data() + ((size_t)b * R + ring_slot(head, t, R)) * n, n * sizeof(double));
-    }
-    void get_linear(const double * src, size_t n, double * out)
-    {
-      set_device(device_id);
-      stream_sync(stream);
-      d2h(out, src, n * sizeof(double), stream);
-      stream_sync(stream);
-    }
     void get_K(double * out, bool all)
     {
       stream_sync(stream);
@@ -1048,40 +831,29 @@ namespace smpc
       d2h(out, dev, n * sizeof(double), stream);
       stream_sync(stream);
     }
-    void get(int what, double * out) override
+    void get_output(Output what, double * out) override
     {
       switch (what)
       {
-      case 0:
+      case OUT_XS:
         return get_ring(buf.xs, D::NX, H + 1, out);
-      case 1:
+      case OUT_US:
         return get_ring(buf.us, D::NU, H, out);
-      case 2:
+      case OUT_K0:
         return get_K(out, false);
-      case 3:
+      case OUT_KS:
         return get_K(out, true);
-      case 4:
+      case OUT_VS:
         return get_ring(buf.vs, D::NC, H, out);
-      case 5:
-      {
-        // device arrays hold lambda_{t+1} at stage t; the API returns lams[0..H] with lams[0] = 0
-        std::vector<double> tmp((size_t)B * H * D::NDX);
-        get_ring(buf.lams, D::NDX, H, tmp.data());
-        for (int b = 0; b < B; b++)
-        {
-          double * o = out + (size_t)b * (H + 1) * D::NDX;
-          std::memset(o, 0, D::NDX * sizeof(double));
-          std::memcpy(o + D::NDX, tmp.data() + (size_t)b * H * D::NDX, (size_t)H * D::NDX * sizeof(double));
-        }
-        return;
-      }
-      case 6:
+      case OUT_LAMS:
+        return get_lams(buf.lams, D::NDX, out);
+      case OUT_XDOT01:
         return get_linear(buf.xdot01, (size_t)B * 4 * D::NV, out);
-      case 7:
+      case OUT_FOOT_REFS:
         return get_linear(buf.foot_ref, (size_t)B * H * D::NF * 3, out);
-      case 8:
+      case OUT_INFO:
         return get_linear(buf.scal, (size_t)B * SC_N, out);
-      case 9:
+      case OUT_CONTACT_FORCES:
         return get_linear(buf.forces, (size_t)B * H * D::NCM, out);
       default:
         throw std::runtime_error("unknown output");
@@ -1183,19 +955,6 @@ namespace smpc
         launch<SimStepArgs<D>, sim_integrate_body<D>, 64, 1, 1>(B, stream, sa);
       }
     }
-    event_t ev_handoff{};
-    bool ev_handoff_valid = false;
-    void wait_stream(stream_t other) override
-    {
-      set_device(device_id);
-      if (!ev_handoff_valid)
-      {
-        ev_handoff = event_create();
-        ev_handoff_valid = true;
-      }
-      event_record(ev_handoff, stream);
-      stream_wait_event(other, ev_handoff);
-    }
     // u = u_interp - K_0 (x_interp (-) x_meas) at `delay` after the last solve (reference examples/go2_fulldynamics.py:271-285)
     void riccati_feedback(double delay, const double * X, double * u_out) override
     {
@@ -1232,12 +991,11 @@ namespace smpc
       d2h(u_out, uo, nu * sizeof(double), stream);
       stream_sync(stream);
     }
-    bool phase_cycles(double * out64) override
+    void phase_cycles(double * out64) override
     {
       if (!buf.dbg)
-        return false;
+        throw std::runtime_error("phase timers are off (set SMPC_PHASE_PROFILE=1 before smpc_create_fulldynamics)");
       get_linear(buf.dbg, 64, out64);
-      return true;
     }
     int lq_size() const override { return D::LQ_STRIDE; }
     void debug_lq(int inst, int t, double * out) override

@@ -165,3 +165,151 @@ def test_status_word_flags_failed_instances(built):
     st = gm.status
     assert st[1] & 1 and st[0] == 0 and st[2] == 0
     assert np.all(np.isfinite(gm.xs[0])) and np.all(np.isfinite(gm.xs[2]))  # the others are untouched
+
+
+# ---- what each handle kind answers where the entry point is not for it (C ABI, CPU tier) ----
+_INVALID, _RUNTIME = -1, -2  # SMPC_ERR_INVALID, SMPC_ERR_RUNTIME (include/smpc.h)
+_KINO_ONLY = b"needs a kinodynamics handle (smpc_create)"
+
+
+def _raw_abi():
+    """The emu library through plain ctypes: every pointer a void *, so that null and foreign pointers can be passed."""
+    S.emu_lib()
+    R = C.CDLL(S.EMU_LIB)
+    R.smpc_last_error.restype = C.c_char_p
+    return R
+
+
+def _answer(R, fn, *args):
+    rc = getattr(R, fn)(*args)
+    return rc, R.smpc_last_error()
+
+
+def test_handle_kinds_answer_foreign_entry_points(built, monkeypatch):
+    """Return code and text of every kind-specific entry point on the handle kinds that do not support it, smpc_get_dims of the three
+    kinds, the slots a centroidal handle reports to smpc_get_kernel_times_n, and the symmetry texts of the three create functions."""
+    monkeypatch.delenv("SMPC_PHASE_PROFILE", raising=False)
+    lib = S.emu_lib()
+    R = _raw_abi()
+    H = 10
+    gk, rb, _, _ = S.make_product(1, lib=lib, horizon=H)
+    gc, _, _, _ = S.make_cent_product(1, lib=lib, horizon=H)
+    gf, _, _, _ = S.make_full_product(1, lib=lib, horizon=H)
+    k, c, f = (C.c_void_p(g._h.value if hasattr(g._h, "value") else g._h) for g in (gk, gc, gf))
+    buf = (C.c_double * 20000)()
+    out, out2 = C.cast(buf, C.c_void_p), C.cast(C.byref(buf, 8 * 10000), C.c_void_p)
+
+    def expect(code, text, fn, *args):
+        rc, msg = _answer(R, fn, *args)
+        assert rc == code and text in msg, (fn, rc, msg)
+
+    # full-dynamics handles only
+    for h in (k, c):
+        expect(_INVALID, b"smpc_get_contact_forces needs a full-dynamics handle", "smpc_get_contact_forces", h, out)
+    # kinodynamics handles only
+    for h in (c, f):
+        expect(_INVALID, _KINO_ONLY, "smpc_gather_outputs", h, out, C.c_size_t(4096))
+        expect(_INVALID, _KINO_ONLY, "smpc_gather_outputs_device", h, out, C.c_size_t(4096))
+        expect(_INVALID, _KINO_ONLY, "smpc_gather_outputs_peer", h, out, 0)
+        expect(_INVALID, b"kinodynamics handles only", "smpc_debug_get_extra_multipliers", h, 0, out)
+    expect(_INVALID, b"the problem has no such rows", "smpc_debug_get_extra_multipliers", k, 0, out)
+    expect(_INVALID, b"the problem has no such rows", "smpc_debug_get_extra_multipliers", k, 1, out)
+    # kinodynamics and full-dynamics handles
+    expect(_INVALID, _KINO_ONLY, "smpc_get_x_device", c, 0, out)
+    expect(_INVALID, b"the centroidal step is one fused kernel", "smpc_set_early_exit_on_tol", c, 1)
+    expect(_INVALID, _KINO_ONLY, "smpc_debug_get_lq", c, 0, 0, out)
+    expect(_INVALID, _KINO_ONLY, "smpc_debug_get_terminal", c, 0, out, out2)
+    mask = (C.c_uint * 1)(15)
+    expect(_INVALID, b"smpc_full_forward_dynamics needs a kinodynamics or a full-dynamics handle", "smpc_full_forward_dynamics", c, 1, out, out,
+           mask, None, None, C.c_double(0), C.c_double(0), 0, out, out2, None, None)
+    contact = (C.c_uint8 * 4)(1, 1, 1, 1)
+    expect(_INVALID, b"smpc_sim_step_device needs a kinodynamics or a full-dynamics handle", "smpc_sim_step_device", c, out, out, contact, None,
+           None, C.c_double(1e-3))
+    # the same index errors carry the code of the handle kind that raises them
+    expect(_INVALID, b"Stage index exceeds stage vector size", "smpc_debug_get_lq", k, 0, H, out)
+    expect(_RUNTIME, b"Stage index exceeds stage vector size", "smpc_debug_get_lq", f, 0, H, out)
+    expect(_INVALID, b"instance index out of range", "smpc_debug_get_terminal", k, 1, out, out2)
+    expect(_RUNTIME, b"instance index out of range", "smpc_debug_get_terminal", f, 1, out, out2)
+    # phase timers are off unless SMPC_PHASE_PROFILE is set when the handle is created
+    for h in (k, c):
+        expect(_INVALID, b"(set SMPC_PHASE_PROFILE=1 before smpc_create)", "smpc_debug_get_phase_cycles", h, out)
+    expect(_RUNTIME, b"(set SMPC_PHASE_PROFILE=1 before smpc_create_fulldynamics)", "smpc_debug_get_phase_cycles", f, out)
+    # smpc_lq_size: the row-major kinodynamics knot unless the handle is a full-dynamics one
+    nk = R.smpc_lq_size(k)
+    assert nk == 6000 and R.smpc_lq_size(c) == nk and R.smpc_lq_size(None) == nk and R.smpc_lq_size(f) == 3848
+    # a controller of the other family
+    kw = dict(kp_base=10.0, kp_posture=1.0, kp_contact=10.0, w_base=10.0, w_posture=0.1, w_contact_force=1e-3, w_contact_motion=1.0)
+    s = O.id_settings(rb, 1e-3, admm_iters=10, admm_tol=-1.0, **kw)
+    mh = simple_mpc.RobotModelHandler(simple_mpc.load_robot("go2_like", lib), "standing", "root_joint")
+    for n in S.FEET:
+        mh.addPointFoot(n, "root_joint")
+    kid = simple_mpc.KinodynamicsID(mh, 1e-3, {n: s[n] for n in simple_mpc.KinodynamicsID._KEYS}, s["tau_max"], s["v_max"], batch=1, lib=lib,
+                                    admm_iters=10, admm_tol=-1.0)
+    idh = C.c_void_p(kid._h.value if hasattr(kid._h, "value") else kid._h)
+    expect(_INVALID, b"a centroidal MPC handle feeds a CentroidalID controller", "smpc_id_set_targets_from_mpc", idh, c, C.c_double(0), 2)
+    gk2, _, _, _ = S.make_product(2, lib=lib, horizon=H)
+    expect(_INVALID, b"must hold the same batch of the same robot", "smpc_id_set_targets_from_mpc", idh, C.c_void_p(gk2._h.value), C.c_double(0), 2)
+    gf2, _, _, _ = S.make_full_product(2, lib=lib, horizon=H)
+    expect(_INVALID, b"must hold the same batch of the same robot", "smpc_id_set_targets_from_mpc", idh, C.c_void_p(gf2._h.value), C.c_double(0), 2)
+
+    # smpc_get_dims: nq nv nx ndx nu nc nfeet H
+    d = (C.c_int * 8)()
+    want = {"kino": [19, 18, 37, 36, 24, 24, 4, H], "cent": [19, 18, 9, 9, 12, 8, 4, H], "full": [19, 18, 37, 36, 12, 24, 4, H]}
+    for name, h in (("kino", k), ("cent", c), ("full", f)):
+        assert R.smpc_get_dims(h, d) == 0 and list(d) == want[name], (name, list(d))
+
+    # kernel-time slots of a centroidal handle: its six kernels of a point-foot control step, 0 in the slots behind them
+    assert R.smpc_kernel_time_slots() == 9
+    gc.generateCycleHorizon(O.trot_cycle())
+    gc.switchToWalk(np.array([0.2, 0, 0, 0, 0, 0.0]))
+    gc.iterate(S.random_states(rb, 1))
+    ms_, calls = (C.c_double * 12)(*([-1.0] * 12)), (C.c_long * 12)(*([-1] * 12))
+    assert R.smpc_get_kernel_times_n(c, ms_, calls, 12) == 0
+    assert [int(v > 0) for v in calls[:9]] == [1, 1, 1, 1, 1, 1, 0, 0, 0] and list(calls[6:9]) == [0, 0, 0] and list(ms_[6:9]) == [0.0, 0.0, 0.0]
+    assert list(calls[9:]) == [-1, -1, -1] and list(ms_[9:]) == [-1.0, -1.0, -1.0]  # (at most smpc_kernel_time_slots() entries are written)
+    calls[0] = calls[1] = calls[2] = -1
+    assert R.smpc_get_kernel_times_n(c, ms_, calls, 2) == 0 and calls[0] > 0 and calls[1] > 0 and calls[2] == -1
+    assert R.smpc_reset_kernel_times(c) == 0 and R.smpc_get_kernel_times_n(c, ms_, calls, 9) == 0 and list(calls[:9]) == [0] * 9
+
+    # symmetry of the weights: the kinodynamics create function names the matrix, the others do not
+    def asym(w):
+        w = np.array(w, float)
+        w[0, 1] += 1.0
+        return w
+
+    sk = O.go2_kino_settings(rb)
+    with pytest.raises(RuntimeError, match="w_x must be symmetric"):
+        S.make_product(1, lib=lib, horizon=H, settings_override={"w_x": asym(sk["w_x"])})
+    with pytest.raises(RuntimeError, match="w_u must be symmetric"):
+        S.make_product(1, lib=lib, horizon=H, settings_override={"w_u": asym(sk["w_u"])})
+    with pytest.raises(RuntimeError, match="weight matrices must be symmetric"):
+        S.make_cent_product(1, lib=lib, horizon=H, settings_override={"w_u": asym(O.go2_centroidal_settings(rb)["w_u"])})
+    with pytest.raises(RuntimeError, match="weight matrices must be symmetric"):
+        S.make_full_product(1, lib=lib, horizon=H, settings_override={"w_x": asym(O.go2_full_settings(rb)["w_x"])})
+    rbt = O.Robot("talos_like")
+    with pytest.raises(RuntimeError, match="weight matrices must be symmetric"):
+        S.make_talos_kino_product(1, lib=lib, horizon=H, settings_override={"w_x": asym(O.talos_kino_settings(rbt)["w_x"])})
+
+
+def test_null_handle_is_an_invalid_argument_everywhere(built):
+    """Every MPC entry point that takes a handle and an output answers a null one with SMPC_ERR_INVALID "null argument" (the getters of the
+    trajectories, the info block and the debug read-outs used to dereference it)."""
+    R = _raw_abi()
+    buf = (C.c_double * 64)()
+    out = C.cast(buf, C.c_void_p)
+    for fn in ("smpc_get_xs", "smpc_get_us", "smpc_get_vs", "smpc_get_lams", "smpc_get_K0", "smpc_get_Ks", "smpc_get_state_derivative01",
+               "smpc_get_reference_poses", "smpc_get_info", "smpc_get_contact_forces", "smpc_debug_get_phase_cycles"):
+        assert _answer(R, fn, None, out) == (_INVALID, b"null argument"), fn
+    assert _answer(R, "smpc_debug_get_extra_multipliers", None, 0, out) == (_INVALID, b"null argument")
+    assert _answer(R, "smpc_debug_get_lq", None, 0, 0, out) == (_INVALID, b"null argument")
+    assert _answer(R, "smpc_debug_get_steps", None, out, out) == (_INVALID, b"null argument")
+    assert _answer(R, "smpc_debug_get_terminal", None, 0, out, out) == (_INVALID, b"null argument")
+    assert _answer(R, "smpc_get_cold_trace", None, out, 4) == (_INVALID, b"null argument")
+    assert _answer(R, "smpc_set_profiling", None, 1) == (_INVALID, b"null argument")
+    assert _answer(R, "smpc_reset_kernel_times", None) == (_INVALID, b"null argument")
+    # ... and a null output on a live handle
+    gk, _, _, _ = S.make_product(1, lib=S.emu_lib(), horizon=10)
+    k = C.c_void_p(gk._h.value)
+    for fn in ("smpc_get_xs", "smpc_get_us", "smpc_get_info", "smpc_debug_get_phase_cycles"):
+        assert _answer(R, fn, k, None) == (_INVALID, b"null argument"), fn
+    assert R.smpc_get_cold_trace(k, None, 0) > 0  # (the count alone may still be asked for)
