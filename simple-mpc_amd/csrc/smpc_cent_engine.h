@@ -1,5 +1,6 @@
-// smpc_cent_engine.h -- host side of the batched centroidal MPC: the reference's MPC class (smpc_engine.h cites it line
-// by line) over a CentroidalOCP (reference src/centroidal-dynamics.cpp).  One control step = two launches:
+// smpc_cent_engine.h -- host side of the batched centroidal MPC: the reference's MPC class (smpc_stage_engine.h cites it line
+// by line; the stage that enters the horizon is MpcEngineBase::recede_horizon for all three engines) over a CentroidalOCP
+// (reference src/centroidal-dynamics.cpp).  One control step = two launches:
 //   frontend_body   measured multibody states -> getCentroidalState + foot positions (src/mpc.cpp:192,200)
 //   cent_step_body  recede + references + k ProxDDP iterations, one wavefront per instance (smpc_cent_kernels.h)
 // What differs from the kinodynamics host logic:
@@ -489,23 +490,7 @@ namespace smpc
       ref_rot.reset(); // (every control step rewrites every stage's reference pose with the identity rotation: src/mpc.cpp:303-309)
       if (cycle.empty())
         throw std::runtime_error("generateCycleHorizon must be called before iterate");
-      int last_support = 0;
-      for (int f = 0; f < DC::NF; f++)
-        last_support += (horizon[H - 1].mask >> f) & 1u;
-      CentStage<DC> incoming;
-      if (walking || last_support < DC::NF)
-      {
-        incoming = cycle[0];
-        std::rotate(cycle.begin(), cycle.begin() + 1, cycle.end());
-        timer.recede_cycle();
-      }
-      else
-      {
-        incoming = standing;
-        timer.update_timing(true);
-      }
-      horizon.erase(horizon.begin());
-      horizon.push_back(incoming);
+      recede_horizon(horizon, cycle, standing, DC::NF);
       // setReferenceState(H-1, x_reference_) ; setVelocityBase(H-1, velocity_base_): momentum references are m v
       for (int i = 0; i < 3; i++)
       {

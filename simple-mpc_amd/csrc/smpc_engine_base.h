@@ -2,6 +2,7 @@
 // engines share as data and as host code, and the virtual entry points the C ABI calls.  No kernel lives here.
 #pragma once
 #include "smpc_solver_kernels.h"
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <utility>
@@ -453,6 +454,30 @@ namespace smpc
       for (int i = 0; i < 6; i++)
         velocity_base[i] = V[i];
       upload_velocity(vbase_dev, V, false);
+    }
+
+    // MPC::recedeWithCycle on the host, shared by the batch (src/mpc.cpp:220-254): the stage that enters the horizon is the next one of the
+    // cycle while walking -- or until every foot of the last stage is in support --, the standing stage after that
+    template <class Stage>
+    void recede_horizon(std::vector<Stage> & horizon, std::vector<Stage> & cycle, const Stage & standing, int nf)
+    {
+      int last_support = 0;
+      for (int f = 0; f < nf; f++)
+        last_support += (horizon[H - 1].mask >> f) & 1u;
+      Stage incoming;
+      if (walking || last_support < nf)
+      {
+        incoming = cycle[0];
+        std::rotate(cycle.begin(), cycle.begin() + 1, cycle.end());
+        timer.recede_cycle();
+      }
+      else
+      {
+        incoming = standing;
+        timer.update_timing(true);
+      }
+      horizon.erase(horizon.begin());
+      horizon.push_back(incoming);
     }
 
     // ---- what differs per problem ----
