@@ -48,6 +48,9 @@ namespace smpc
     static constexpr int O_lpd = O_lu + NU;
     static constexpr int O_vpd = O_lpd + NDX;
     static constexpr int O_act = O_vpd + NC;
+    // INVARIANT of O_cdirty (single writer, as FullDims::O_cdirty in smpc_full_model.h):
+    // cent6_deriv_body is the only writer of the dense rows and of this flag; flag == 0
+    // must mean "the rows are exactly zero".  A new writer of lq has to keep that.
     static constexpr int O_cdirty = O_act + NC;    // 1.0 while the dense rows [C | D] of this block hold a nonzero entry (cent6_deriv_body; allocations are zero-filled)
     static constexpr int LQ_STRIDE = ((O_cdirty + 1 + 7) / 8) * 8;
     static constexpr int G_K = 0;

@@ -81,6 +81,11 @@ namespace smpc
     static constexpr int O_act = O_vpd + NC;        // 1.0 / 0.0 activity of all NC rows (box rows, then the dense cone rows)
     // 1.0 while the dense cone rows [Cd | Dd] of this block hold a nonzero row (fdyn_deriv_body: a stage without an active cone row writes its rows --
     // zeros -- only over a block that is not zero already; fresh allocations are zero-filled)
+    // INVARIANT of O_cdirty (single writer): fdyn_deriv_body is the ONLY writer of rows [0, NCONE) of O_C / O_D and of this flag; every write of
+    // a nonzero row sets the flag in the same pass, and the flag returns to 0.0 only in the pass that has overwritten the rows with zeros.  The
+    // sweeps read the block unconditionally, so flag == 0 must mean "the block is exactly zero".  A new writer of lq (a cross-check kernel, an
+    // lq initialiser, a load_state that restores lq) or an allocator that does not zero-fill must keep the flag equal to "the block holds a
+    // nonzero entry" (tests/test_sweeps.py asserts exactly that after every control step, through debug_lq).
     static constexpr int O_cdirty = O_act + NC;
     static constexpr int LQ_STRIDE = ((O_cdirty + 1 + 7) / 8) * 8;
     // gains block per (instance, stage)

@@ -1070,13 +1070,13 @@ class BatchedMPC:
         )
         if isinstance(self.ocp_handler, FullDynamicsOCP):
             # full-dynamics knot (smpc_full_model.h): the box rows are unit selectors kept as activity flags; Cd / Dd hold the
-            # dense cone rows of 6-D feet only
+            # dense rows (cone rows, then land rows); cdirty is the scalar flag "Cd / Dd hold a nonzero entry" (FullDims::O_cdirty)
             nbox = 2 * nu
             ncone = nc - nbox
             layout = (
                 ("A", (ndx, ndx)), ("B", (ndx, nu)), ("Q", (ndx, ndx)), ("S", (ndx, nu)), ("R", (nu, nu)), ("Cd", (ncone, ndx)),
                 ("Dd", (ncone, nu)), ("q", (ndx,)), ("r", (nu,)), ("f", (ndx,)), ("d", (nc,)), ("lx", (ndx,)), ("lu", (nu,)),
-                ("lpd", (ndx,)), ("vpd", (nc,)), ("act", (nc,)),
+                ("lpd", (ndx,)), ("vpd", (nc,)), ("act", (nc,)), ("cdirty", ()),
             )
         elif int(self.ocp_handler.settings.get("force_size", 3)) == 6 and isinstance(self.ocp_handler, KinodynamicsOCP):
             # kinodynamics OCP with 6-D feet on the dense stage kernels (FullDims<..., KIN = 1>): rows [u box (absent) | joint box | 17 wrench-cone
@@ -1086,7 +1086,7 @@ class BatchedMPC:
             layout = (
                 ("A", (ndx, ndx)), ("B", (ndx, nu)), ("Q", (ndx, ndx)), ("S", (ndx, nu)), ("R", (nu, nu)), ("Cd", (ncone, ndx)),
                 ("Dd", (ncone, nu)), ("Cv", (nvel, ndx)), ("q", (ndx,)), ("r", (nu,)), ("f", (ndx,)), ("d", (nc,)), ("lx", (ndx,)),
-                ("lu", (nu,)), ("lpd", (ndx,)), ("vpd", (nc,)), ("act", (nc,)),
+                ("lu", (nu,)), ("lpd", (ndx,)), ("vpd", (nc,)), ("act", (nc,)), ("cdirty", ()),
             )
         for name, shape in layout:
             sz = int(np.prod(shape))

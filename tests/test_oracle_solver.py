@@ -6,6 +6,7 @@ import scipy.linalg as sla
 
 import oracle_lib as O
 import mpc_setup as S
+from sweep_check import dense_kkt as _dense_kkt
 
 
 def _random_lq(rng, H, ndx, nu, nc, mu):
@@ -24,58 +25,6 @@ def _random_lq(rng, H, ndx, nu, nc, mu):
     f, d = rng.normal(size=(H, ndx)) * 0.1, rng.normal(size=(H, nc)) * 0.1
     QN, qN = spd(ndx), rng.normal(size=ndx)
     return Q, S_, R, q, r, A, B, f, Cm, D, d, QN, qN
-
-
-def _dense_kkt(Q, S_, R, q, r, A, B, f, Cm, D, d, QN, qN, mu):
-    H, ndx, nu = B.shape
-    nc = Cm.shape[1]
-    per = nu + nc + 2 * ndx
-    N = H * per
-    K = np.zeros((N, N))
-    rhs = np.zeros(N)
-    iu = lambda t: t * per
-    iv = lambda t: t * per + nu
-    il = lambda t: t * per + nu + nc
-    ix = lambda t: t * per + nu + nc + ndx
-    for t in range(H):
-        r0 = iu(t)
-        K[r0:r0 + nu, iu(t):iu(t) + nu] = R[t]
-        K[r0:r0 + nu, il(t):il(t) + ndx] = B[t].T
-        K[r0:r0 + nu, iv(t):iv(t) + nc] = D[t].T
-        if t > 0:
-            K[r0:r0 + nu, ix(t - 1):ix(t - 1) + ndx] = S_[t].T
-        rhs[r0:r0 + nu] = -r[t]
-        r0 = iv(t)
-        K[r0:r0 + nc, iv(t):iv(t) + nc] = -mu * np.eye(nc)
-        K[r0:r0 + nc, iu(t):iu(t) + nu] = D[t]
-        if t > 0:
-            K[r0:r0 + nc, ix(t - 1):ix(t - 1) + ndx] = Cm[t]
-        rhs[r0:r0 + nc] = -d[t]
-        r0 = il(t)
-        K[r0:r0 + ndx, iu(t):iu(t) + nu] = B[t]
-        K[r0:r0 + ndx, ix(t):ix(t) + ndx] = -np.eye(ndx)
-        K[r0:r0 + ndx, il(t):il(t) + ndx] = -mu * np.eye(ndx)
-        if t > 0:
-            K[r0:r0 + ndx, ix(t - 1):ix(t - 1) + ndx] = A[t]
-        rhs[r0:r0 + ndx] = -f[t]
-        r0 = ix(t)
-        K[r0:r0 + ndx, il(t):il(t) + ndx] = -np.eye(ndx)
-        if t + 1 < H:
-            K[r0:r0 + ndx, ix(t):ix(t) + ndx] = Q[t + 1]
-            K[r0:r0 + ndx, iu(t + 1):iu(t + 1) + nu] = S_[t + 1]
-            K[r0:r0 + ndx, il(t + 1):il(t + 1) + ndx] = A[t + 1].T
-            K[r0:r0 + ndx, iv(t + 1):iv(t + 1) + nc] = Cm[t + 1].T
-            rhs[r0:r0 + ndx] = -q[t + 1]
-        else:
-            K[r0:r0 + ndx, ix(t):ix(t) + ndx] = QN
-            rhs[r0:r0 + ndx] = -qN
-    assert np.abs(K - K.T).max() < 1e-12
-    z = sla.solve(K, rhs)
-    dx = np.stack([np.zeros(ndx)] + [z[ix(t):ix(t) + ndx] for t in range(H)])
-    du = np.stack([z[iu(t):iu(t) + nu] for t in range(H)])
-    dv = np.stack([z[iv(t):iv(t) + nc] for t in range(H)])
-    dl = np.stack([np.zeros(ndx)] + [z[il(t):il(t) + ndx] for t in range(H)])
-    return dx, du, dv, dl
 
 
 def test_prox_riccati_vs_dense_kkt():

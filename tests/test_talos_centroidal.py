@@ -26,6 +26,12 @@ def _loop(om, gm, rb, steps, B=2, expect_cones=False, tol=TOL):
         a, b = np.array(om.cold_trace()), np.array(gm.cold_trace())
         flips = a[:, 3] != b[:, 3]
         assert flips.any() and (a[flips, 2] < 1e-5).all() and e0 < 100 * tol, (e0, a, b)
+        # ... and up to the flip both sides are the same solve: every trace entry up to and including the iterate the flipped step starts from
+        # (merit, primal and dual residual at that iterate) agrees at tol, as do the step sizes before it
+        k = int(np.flatnonzero(flips)[0])
+        for c in range(3):  # column by column: the residual columns must not hide behind the merit
+            assert np.abs(a[:k + 1, c] - b[:k + 1, c]).max() <= tol * np.abs(a[:k + 1, c]).max(), (k, c, a, b)
+        assert np.array_equal(a[:k, 3], b[:k, 3]), (k, a, b)
     worst, cones, backtracked = 0.0, 0, 0
     for step in range(steps):
         X = S.talos_random_states(rb, B, seed=step, scale=0.5)

@@ -121,7 +121,12 @@ def test_emulated_kernels_stage_knots(built):
         for t in (0, 3, 12, 19):
             ko, kg = om.knot(0, t), gm.debug_lq(0, t)
             # (r carries D^T nu: the multipliers are residuals / mu, their rounding times 1e8; f = mu (lam+ - lam) of the second iterate of a
-            #  scenario with dozens of active cone rows: 0.9e-10 .. 1.1e-10 depending on the rounding of the sweep that made the iterate)
+            #  scenario with dozens of active cone rows: 0.9e-10 .. 1.1e-10 depending on the rounding of the sweep that made the iterate.
+            #  Why these two gates are not the 1e-10 / 1e-11 they once were: both quantities are evaluated at the SECOND iterate of either
+            #  side, i.e. behind one Newton step of a problem whose folded Q carries Cv^T Cv / mu = 1e8: tests/sweep_check.py measures that two
+            #  CPU FP64 solves of this scenario's knots differ by 1.3e-7 (dxs) and 1.4e-6 (dus) per stage, the device from the Riccati
+            #  reference by 1.1e-9 / 2.6e-9 -- an iterate gap of that order times |df/dx|, |dCv/dx| is what f (observed up to 1.1e-10 before,
+            #  hence 3e-10) and Cv (1e-11 .. 3e-11, hence 1e-10) see.  The sweep checker gives no ground for a tighter gate here.)
             for k in ("A", "B", "S", "R", "f", "r"):
                 assert S.rel_err(ko[k], kg[k]) < (1e-7 if k == "r" else (3e-10 if k == "f" else 1e-10)), (t, k, S.rel_err(ko[k], kg[k]))
             # the frame-velocity rows: the oracle keeps their multipliers explicit, the stage kernel folds them (Q += Cv^T Cv / mu)
