@@ -5,6 +5,7 @@
 // reference (src/kinodynamics.cpp:175,235,279; src/ocp-handler.cpp:28,32,76).
 #pragma once
 #include "../smpc.h"
+#include <algorithm>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -304,6 +305,10 @@ namespace simple_mpc
       return buf;
     }
     void loadState(const std::vector<unsigned char> & buf) { check(smpc_load_state(h_, buf.data(), buf.size())); }
+    // reset instances to the cold start: solver state as the constructor left it, problem data untouched (smpc_reset_instances).  A host
+    // list (unsorted, duplicates allowed), or a uint8 mask [batch] in device memory that must stay valid until wait()
+    void resetInstances(const int * instances, int n) { check(smpc_reset_instances(h_, instances, n)); }
+    void resetInstancesDevice(const uint8_t * mask_device) { check(smpc_reset_instances_device(h_, mask_device)); }
     std::vector<int> getFootTakeoffCycle(const std::string & ee) { return timing(ee, 0); }
     std::vector<int> getFootLandCycle(const std::string & ee) { return timing(ee, 1); }
     smpc_handle * handle() { return h_; }
@@ -424,6 +429,23 @@ namespace simple_mpc
     {
       for (auto & p : parts_)
         p->switchToStand();
+    }
+    // a list of GLOBAL instance indices (unsorted, duplicates allowed), every index handed to the part that owns the instance; an index
+    // outside [0, batch) throws before any part is touched
+    void resetInstances(const int * instances, int n)
+    {
+      std::vector<std::vector<int>> local(parts_.size());
+      for (int k = 0; k < n; k++)
+      {
+        const int g = instances[k];
+        if (g < 0 || g >= batch_)
+          throw std::runtime_error("BatchedMPCGroup::resetInstances: instance index out of range");
+        const int i = (int)(std::upper_bound(first_.begin(), first_.end(), g) - first_.begin()) - 1;
+        local[i].push_back(g - first_[i]);
+      }
+      for (int i = 0; i < parts(); i++)
+        if (!local[i].empty())
+          parts_[i]->resetInstances(local[i].data(), (int)local[i].size());
     }
     // X: [batch][nx] measured states; out: [batch][gatherRow()] rows [x1 | u0 | K0] (both caller-owned; they must stay valid until this
     // returns).  All devices work concurrently; returns when every part is complete.

@@ -244,6 +244,23 @@ int smpc_gather_outputs_peer(smpc_handle * h, double * out_peer, int dst_device)
 int smpc_state_size(smpc_handle * h, size_t * bytes);
 int smpc_save_state(smpc_handle * h, void * buffer, size_t capacity, size_t * written);
 int smpc_load_state(smpc_handle * h, const void * buffer, size_t size);
+/* Reset single instances of the batch to the cold start (the reference has no such call: one MPC object is one robot, and a user
+ * constructs a new one).  After a reset, the solver state of the instance is what the constructor left in it; the problem data are
+ * untouched.  Solver state: xs, us, vs, lams, the augmented-Lagrangian centres, the per-instance scalars of smpc_get_info (hence the
+ * status word: 0), the line-search selection, the state derivatives of stages 0, 1 and the swing start / end of every foot -- written
+ * relative to the current ring head, so that a reset at any control step gives the same trajectory t = 0 .. H.  Problem data: the
+ * instance's velocity command and its references, the shared stage list, gait timers, walking / standing state, reference poses and
+ * the two switches (early exit, retained state derivatives).  The cold solution is a function of the settings only: it is kept on the
+ * device by every handle and is not part of the checkpoint.  With smpc_set_retain_state_derivatives on, the getters of every stage
+ * refuse after a reset until the next iterate, as after smpc_load_state.
+ *   smpc_reset_instances          re-applies src/mpc.cpp:72-89 to the n instances of a host list (unsorted, duplicates allowed); an index
+ *                                 outside [0, B) returns SMPC_ERR_INVALID and changes nothing; n = 0 succeeds and does nothing.  The mask
+ *                                 is built on the host and uploaded on the handle's stream, then as below
+ *   smpc_reset_instances_device   re-applies src/mpc.cpp:72-89 to every instance with a non-zero byte in mask_device [B] (device memory):
+ *                                 one kernel on the handle's stream, no host synchronisation -- a fall detector on the device writes the
+ *                                 mask and nothing crosses the host.  The kernel reads the mask: it must stay valid until smpc_wait */
+int smpc_reset_instances(smpc_handle * h, const int * instances, int n);
+int smpc_reset_instances_device(smpc_handle * h, const uint8_t * mask_device);
 /* xs_[t] of every instance into a dense device buffer [B][nx]; asynchronous on the handle's stream.
  * Lets a closed loop keep the measured states resident in HBM (x_meas = xs[1] + noise). */
 int smpc_get_x_device(smpc_handle * h, int t, double * out_device);
@@ -271,7 +288,7 @@ int smpc_get_state_derivative01(smpc_handle * h, double * out);
  *   smpc_get_state_derivatives          out [B][H][dim] (host); dim = 2 nv (kinodynamics, full dynamics), 9 (centroidal)
  *   smpc_get_state_derivatives_device   the same into a device buffer, asynchronous on the handle's stream
  * The getters return SMPC_ERR_INVALID when the switch is off, when no iterate has run since it was enabled, and after smpc_load_state
- * until the next iterate (the buffer is not part of the checkpoint: smpc_state_size does not change).  Stages 0, 1 equal
+ * or smpc_reset_instances until the next iterate (the buffer is not part of the checkpoint: smpc_state_size does not change).  Stages 0, 1 equal
  * smpc_get_state_derivative01. */
 int smpc_set_retain_state_derivatives(smpc_handle * h, int on);
 int smpc_get_state_derivatives(smpc_handle * h, double * out);

@@ -35,7 +35,8 @@ struct smpc_handle
   {
     XDOT_NONE,  // no iterate since the switch was enabled
     XDOT_VALID, // filled by the last iterate
-    XDOT_STALE  // smpc_load_state since the last iterate (the buffer is not part of the checkpoint)
+    XDOT_STALE, // smpc_load_state since the last iterate (the buffer is not part of the checkpoint)
+    XDOT_RESET  // smpc_reset_instances since the last iterate (the buffer still holds the derivatives of the iterate before the reset)
   } xdot_state = XDOT_NONE;
   ~smpc_handle()
   {
@@ -162,6 +163,9 @@ namespace
     if (h->xdot_state == smpc_handle::XDOT_STALE)
       return "smpc_load_state has run since the last iterate: the state derivatives retained by smpc_set_retain_state_derivatives are "
              "not part of the checkpoint; run iterate first";
+    if (h->xdot_state == smpc_handle::XDOT_RESET)
+      return "smpc_reset_instances has run since the last iterate: the state derivatives retained by smpc_set_retain_state_derivatives are "
+             "those of the iterate before the reset; run iterate first";
     return nullptr;
   }
 } // namespace
@@ -560,6 +564,27 @@ extern "C"
     if (h->xdot_state == smpc_handle::XDOT_VALID)
       h->xdot_state = smpc_handle::XDOT_STALE;
     return guarded([&] { state_pass(h, StateIO::LOAD, const_cast<void *>(buffer), size); });
+  }
+  // (both forms re-apply the constructor's cold start, reference src/mpc.cpp:72-89, to the chosen instances)
+  int smpc_reset_instances(smpc_handle * h, const int * instances, int n)
+  {
+    if (!h || (!instances && n > 0))
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] {
+      h->e->reset_instances(instances, n);
+      if (n > 0 && h->xdot_state == smpc_handle::XDOT_VALID)
+        h->xdot_state = smpc_handle::XDOT_RESET;
+    });
+  }
+  int smpc_reset_instances_device(smpc_handle * h, const uint8_t * mask_device)
+  {
+    if (!h || !mask_device)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] {
+      h->e->reset_instances_device(mask_device);
+      if (h->xdot_state == smpc_handle::XDOT_VALID)
+        h->xdot_state = smpc_handle::XDOT_RESET;
+    });
   }
   int smpc_get_x_device(smpc_handle * h, int t, double * out_device)
   {

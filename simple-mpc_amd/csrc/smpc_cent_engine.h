@@ -249,6 +249,7 @@ namespace smpc
       dev_free(buf.stages);
       dev_free(buf.model);
       dev_free(fk.model);
+      dev_free(cold.dev);
     }
 
     void upload_stages()
@@ -459,7 +460,21 @@ namespace smpc
       }
       for (int i = 0; i < CKID_N; i++)
         kernel_calls[i] = 0;
+      // instance 0 as the cold solve left it, kept for reset_instances_device (every instance holds the same; DESIGN.md "Resetting single
+      // instances" classifies every buffer)
+      cold.begin(B, H, R, (size_t)R * (2 * 9 + DC::NU + 2 * DC::NC + 9) + SC_N + 18 + DC::NF * 6);
+      cold.retain(buf.xs, 9, RESET_RING, stream);
+      cold.retain(buf.us, DC::NU, RESET_RING, stream);
+      cold.retain(buf.vs, DC::NC, RESET_RING, stream);
+      cold.retain(buf.lams, 9, RESET_RING, stream);
+      cold.retain(buf.vs_e, DC::NC, RESET_RING, stream);
+      cold.retain(buf.lams_e, 9, RESET_RING, stream);
+      cold.retain(buf.scal, SC_N, RESET_INST, stream);
+      cold.retain(buf.xdot01, 18, RESET_INST, stream);
+      cold.retain(buf.ftraj, DC::NF * 6, RESET_INST, stream);
+      stream_sync(stream);
     }
+    void reset_instances_device(const uint8_t * mask_dev) override { launch_reset(mask_dev); }
 
     void generate_cycle_horizon(const unsigned char * cs, int n) override
     {

@@ -2,7 +2,10 @@
 // engines share as data and as host code, and the virtual entry points the C ABI calls.  No kernel lives here.
 #pragma once
 #include "smpc_solver_kernels.h"
+#include "smpc_reset.h"
+#include "smpc_reset_mask.h"
 #include <algorithm>
+#include <cstdint>
 #include <cstring>
 #include <string>
 #include <utility>
@@ -257,6 +260,9 @@ namespace smpc
     size_t stage_out_bytes = 0;
     event_t ev_handoff{};
     bool ev_handoff_valid = false;
+    ColdSolution cold; // one instance's copy of the constructor's cold solve (smpc_reset.h); its block is released with the engine's buffers
+    unsigned char * reset_mask_dev = nullptr; // [B] mask of reset_instances (the host-list form), allocated on first use
+    UploadRing reset_mask_ring;
 
     MpcEngineBase(const HostMpcSettings & ms_, int batch, int device) : B(batch), H(ms_.T), R(ms_.T + 1), device_id(device), ms(ms_) {}
     MpcEngineBase(const MpcEngineBase &) = delete;
@@ -265,6 +271,7 @@ namespace smpc
     virtual ~MpcEngineBase()
     {
       dev_free(stage_out);
+      dev_free(reset_mask_dev);
       if (ev_handoff_valid)
         event_destroy(ev_handoff);
       if (stream_open)
@@ -456,6 +463,36 @@ namespace smpc
       upload_velocity(vbase_dev, V, false);
     }
 
+    // ---- reset of single instances to the cold start (re-applies what the constructor did, reference src/mpc.cpp:72-89) ----
+    // the solver state of the instances with a non-zero byte in mask_dev [B] (device) becomes what the constructor left, relative to the
+    // current ring head; the problem data stay.  One launch on the handle's stream, no host synchronisation.
+    void launch_reset(const unsigned char * mask_dev, int * ls_sel = nullptr, int ls_sel0 = 0)
+    {
+      set_device(device_id);
+      ResetArgs a = cold.plan;
+      a.mask = mask_dev;
+      a.head = head;
+      a.ls_sel = ls_sel;
+      a.ls_sel0 = ls_sel0;
+      launch<ResetArgs, reset_body, 64>(B * R, stream, a);
+    }
+    // the same for a host list of instances (unsorted, duplicates allowed): mask built here, uploaded on the stream
+    void reset_instances(const int * idx, int n)
+    {
+      if (n < 0)
+        throw InvalidCall("smpc_reset_instances: negative count");
+      if (n == 0)
+        return;
+      std::vector<unsigned char> m((size_t)B);
+      if (reset_mask_from_list(idx, n, B, m.data()) >= 0)
+        throw InvalidCall("smpc_reset_instances: instance index out of range");
+      set_device(device_id);
+      if (!reset_mask_dev)
+        reset_mask_dev = (unsigned char *)dev_alloc((size_t)B);
+      reset_mask_ring.upload(reset_mask_dev, m.data(), (size_t)B, stream); // (pinned staging: the caller's queue is not drained)
+      reset_instances_device(reset_mask_dev);
+    }
+
     // MPC::recedeWithCycle on the host, shared by the batch (src/mpc.cpp:220-254): the stage that enters the horizon is the next one of the
     // cycle while walking -- or until every foot of the last stage is in support --, the standing stage after that
     template <class Stage>
@@ -497,6 +534,7 @@ namespace smpc
     virtual void state_derivatives(double * out) = 0; // xdot of every stage at the last solve's iterate, [B][H][xdot_doubles() / (B H)] (device, handle's stream)
     virtual size_t xdot_doubles() const { return (size_t)B * H * 2 * dims[1]; }
     virtual void get_output(Output what, double * out) = 0;
+    virtual void reset_instances_device(const uint8_t * mask_dev) = 0; // smpc_reset_instances_device
     virtual void debug_steps(double * dxs, double * dus) = 0;
 
     // ---- what only some handle kinds have: the others answer SMPC_ERR_INVALID with the text below ----

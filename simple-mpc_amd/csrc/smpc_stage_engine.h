@@ -109,6 +109,7 @@ namespace smpc
         dev_free(und_part[i]);
       dev_free(buf.stages);
       dev_free(buf.model);
+      dev_free(cold.dev);
     }
 
     // ---- what an engine supplies ----
@@ -341,7 +342,37 @@ namespace smpc
       for (int f = 0; f < D::NF; f++)
         for (int i = 0; i < 3; i++)
           ref_foot_pos[f][i] = ft[f * 6 + i];
+      retain_cold();
     }
+    // Instance 0 as the cold solve left it, kept for reset_instances_device: what the broadcast above gave every instance, and the rest
+    // of the solver state a later iterate reads (DESIGN.md "Resetting single instances" classifies every buffer)
+    int cold_ls_sel = 0;
+    void retain_cold()
+    {
+      const size_t Rs = (size_t)R, Hs = (size_t)H;
+      const int fd = buf.forces ? force_doubles() : 0, ne = buf.es ? 2 * D::NF : 0, nl = buf.ls ? D::NF : 0, n3 = buf.vN ? 3 : 0;
+      cold.begin(B, H, R, Rs * (D::NX + D::NU + 2 * D::NC + 2 * D::NDX + 2 * ne + 2 * nl) + Hs * fd + SC_N + 4 * D::NV + D::NF * 6 + 3 * n3);
+      cold.retain(buf.xs, D::NX, RESET_RING, stream);
+      cold.retain(buf.us, D::NU, RESET_RING, stream);
+      cold.retain(buf.vs, D::NC, RESET_RING, stream);
+      cold.retain(buf.lams, D::NDX, RESET_RING, stream);
+      cold.retain(buf.vs_e, D::NC, RESET_RING, stream);
+      cold.retain(buf.lams_e, D::NDX, RESET_RING, stream);
+      cold.retain(buf.es, ne, RESET_RING, stream);
+      cold.retain(buf.es_e, ne, RESET_RING, stream);
+      cold.retain(buf.ls, nl, RESET_RING, stream);
+      cold.retain(buf.ls_e, nl, RESET_RING, stream);
+      cold.retain(buf.forces, fd, RESET_STAGE, stream);
+      cold.retain(buf.scal, SC_N, RESET_INST, stream);
+      cold.retain(buf.xdot01, 4 * D::NV, RESET_INST, stream);
+      cold.retain(buf.ftraj, D::NF * 6, RESET_INST, stream);
+      cold.retain(buf.vN, n3, RESET_INST, stream);
+      cold.retain(buf.vN_e, n3, RESET_INST, stream);
+      cold.retain(buf.dcm_ref, n3, RESET_INST, stream);
+      d2h(&cold_ls_sel, buf.ls_sel, sizeof(int), stream);
+      stream_sync(stream);
+    }
+    void reset_instances_device(const uint8_t * mask_dev) override { launch_reset(mask_dev, buf.ls_sel, cold_ls_sel); }
 
     void generate_cycle_horizon(const unsigned char * cs, int n) override
     {

@@ -822,6 +822,17 @@ class BatchedMPC:
         buf = np.frombuffer(blob, np.uint8).copy()
         self._lib.check(self._lib.L.smpc_load_state(self._h, buf.ctypes.data_as(C.c_void_p), buf.size))
 
+    def resetInstances(self, indices):
+        """Reset the listed instances (any order, duplicates allowed) to the cold start: their solver state becomes what the constructor
+        left, the problem data (velocity commands, references, gait) stay (smpc_reset_instances).  Asynchronous on the handle's stream."""
+        idx = np.ascontiguousarray(list(indices) if not isinstance(indices, np.ndarray) else indices, dtype=np.int32).reshape(-1)
+        self._lib.check(self._lib.L.smpc_reset_instances(self._h, idx, int(idx.size)))
+
+    def reset_instances_device(self, mask_ptr):
+        """The same for every instance with a non-zero byte in a uint8 mask [B] in device memory (smpc_reset_instances_device): one kernel
+        on the handle's stream, nothing crosses the host.  The mask must stay valid until wait()."""
+        self._lib.check(self._lib.L.smpc_reset_instances_device(self._h, C.c_void_p(int(mask_ptr))))
+
     def _get(self, fn, shape):
         out = np.zeros(shape)
         self._lib.check(getattr(self._lib.L, fn)(self._h, out))
