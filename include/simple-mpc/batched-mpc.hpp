@@ -115,7 +115,9 @@ namespace simple_mpc
     }
     // CentroidalOCP(settings, model) + createProblem(getCentroidalState(), T, force_size, gravity, false) + MPC(settings, ocp)
     // (reference src/centroidal-dynamics.cpp:27-37; tests/mpc.cpp:172-258).  iterate() still takes the measured multibody
-    // states [B][nq + nv]; xs_ holds centroidal states [B][H+1][9].
+    // states [B][nq + nv]; xs_ holds centroidal states [B][H+1][9].  `robot` may be any table of smpc_robot.h with 4 point feet (force_size 3)
+    // or 2 flat feet (force_size 6) and up to SMPC_MAX_JOINTS joints -- smpc_create_centroidal validates a caller-filled table and names the
+    // offending field in the exception; every container of this class is sized from smpc_get_dims, so no other type is needed for such a robot.
     BatchedMPC(const smpc_robot_model * robot, const CentroidalSettings & ocp, const MPCSettings & settings, int batch,
                double gravity_arg = -9.81, int device_id = 0)
     : batch_(batch), settings_(settings)

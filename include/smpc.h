@@ -146,7 +146,13 @@ int smpc_create(
  * K0 [B][3 nfeet][9], vs [B][H][2 nfeet] (friction-cone rows), smpc_get_state_derivative01 [B][2][9],
  * smpc_get_reference_poses the contact positions [B][H][nfeet][3], smpc_set_x_reference takes 9 doubles.
  * smpc_get_dims reports nq, nv of the robot and nx = ndx = 9.  Entry points that are specific to the kinodynamics
- * problem (debug_get_lq, debug_get_terminal, get_x_device) fail with SMPC_ERR_INVALID on such a handle. */
+ * problem (debug_get_lq, debug_get_terminal, get_x_device) fail with SMPC_ERR_INVALID on such a handle.
+ * Robots: the OCP depends on the robot through its mass, its feet and the force size only, so ANY table of smpc_robot.h with
+ * (4 feet, force_size 3) or (2 feet, force_size 6) and 2 <= njoints <= SMPC_MAX_JOINTS is accepted.  The two built-in shapes (13 joints /
+ * 4 point feet, 23 joints / 2 flat feet) use the state front end of their stage-kernel family; every other table uses the front end on
+ * the run-time joint tree and is validated before anything is allocated -- parent[0] == -1, 0 <= parent[j] < j, jtype[0] == 0,
+ * jtype[j] in 1..3, nq == njoints + 6, nv == njoints + 5, foot_joint in range, every number finite, masses positive, total_mass equal to
+ * the sum of the masses to 1e-9 relative: SMPC_ERR_INVALID with a message that names the field.  Other foot counts are refused. */
 int smpc_create_centroidal(
   const smpc_robot_model * robot, const smpc_centroidal_settings * ocp, const smpc_mpc_settings * mpc, int batch,
   double gravity_arg, int device_id, smpc_handle ** out);
@@ -377,6 +383,10 @@ int smpc_full_forward_dynamics(
  *      [linear; angular about the CoM], centroidal_state [B][9] = [com; h_lin; h_ang].  Any output may be NULL.
  *      Every kind of handle: the kinodynamics, centroidal and full-dynamics OCPs of the quadruped and of the biped. */
 int smpc_update_internal_data(smpc_handle * h, const double * X, double * feet, double * com, double * hg, double * centroidal_state);
+/* (tests) smpc_update_internal_data computed by the front end on the run-time joint tree (the one a centroidal handle of a robot other
+ * than the two built-in shapes runs in every control step) on the robot table of ANY centroidal handle, the built-in shapes included:
+ * same arguments, same outputs.  Other handle kinds: SMPC_ERR_INVALID. */
+int smpc_debug_frontend_rt(smpc_handle * h, const double * X, double * feet, double * com, double * hg, double * centroidal_state);
 /* Riccati feedback application between MPC knots (reference examples/go2_fulldynamics.py:271-285):
  *   u_out[b] = interpolateLinear(us)[b] - Ks[0][b] * difference(X_meas[b], interpolateState(xs)[b])
  * X_meas [B][nx], u_out [B][nu] (host).  Centroidal handle: X_meas are still the measured multibody states [B][nq + nv];

@@ -6,6 +6,7 @@
 #include "smpc_cent_engine.h"
 #include "smpc_full_engine.h"
 #include "smpc_id.h"
+#include "smpc_robot_check.h"
 #include <cstring>
 #include <memory>
 #include <string>
@@ -272,8 +273,17 @@ extern "C"
     if (ocp->force_size != 3 && ocp->force_size != 6)
       return fail(SMPC_ERR_INVALID, "force size in settings does not match reference force size");
     const bool quad = ocp->force_size == 6;
-    if (quad ? (robot->nfeet != CentTalos::NF || robot->njoints != FullTalos::NJ) : (robot->nfeet != CentGo2::NF || robot->njoints != DimsGo2::NJ))
+    if (robot->nfeet != (quad ? CentTalos::NF : CentGo2::NF))
       return fail(SMPC_ERR_INVALID, "robot shape (njoints, nfeet, force_size) does not match a built kernel instantiation");
+    // the two built shapes keep the front end of their stage-kernel family; every other robot with these feet: the front end on the run-time
+    // joint tree (smpc_frontend_rt.h), on a table that is checked before anything is allocated for it
+    const bool built = robot->njoints == (quad ? FullTalos::NJ : DimsGo2::NJ);
+    if (!built)
+    {
+      const std::string why = robot_table_error(robot);
+      if (!why.empty())
+        return fail(SMPC_ERR_INVALID, why);
+    }
     if (mpc->T < 2)
       return fail(SMPC_ERR_INVALID, "horizon must have at least 2 stages");
     const int nu = ocp->force_size * robot->nfeet;
@@ -297,15 +307,20 @@ extern "C"
     const HostMpcSettings ms = host_mpc(mpc);
     return create_handle(out, [&]() -> MpcEngineBase * {
 #if !defined(SMPC_KINO_ONLY) || defined(SMPC_XCHECK_SUBSET) // (the cross-check HIP build: Go2 kinodynamics + both centroidal engines)
+      if (!built && quad)
+        return new CentEngine<RtDims, CentTalos>(robot, cs, ms, batch, gravity_arg, device_id);
+      if (!built)
+        return new CentEngine<RtDims, CentGo2>(robot, cs, ms, batch, gravity_arg, device_id);
       if (quad)
         return new CentEngine<FullTalos, CentTalos>(robot, cs, ms, batch, gravity_arg, device_id);
       return new CentEngineGo2(robot, cs, ms, batch, gravity_arg, device_id);
 #elif defined(SMPC_CENT_ONLY)
-      if (quad)
+      if (quad || !built)
         throw std::runtime_error("SMPC_CENT_ONLY experiment build");
       return new CentEngineGo2(robot, cs, ms, batch, gravity_arg, device_id);
 #else
       (void)quad;
+      (void)built;
       throw std::runtime_error("SMPC_KINO_ONLY experiment build");
 #endif
     });
@@ -784,6 +799,12 @@ extern "C"
     if (!h || !X)
       return fail(SMPC_ERR_INVALID, "null argument");
     return guarded([&] { h->e->update_internal_data(X, feet, com, hg, centroidal_state); });
+  }
+  int smpc_debug_frontend_rt(smpc_handle * h, const double * X, double * feet, double * com, double * hg, double * centroidal_state)
+  {
+    if (!h || !X)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { h->e->debug_frontend_rt(X, feet, com, hg, centroidal_state); });
   }
   // (a full-dynamics handle: its own robot, 3-D or 6-D contacts, Kp / Kd of force_size entries)
   int smpc_full_forward_dynamics(

@@ -16,6 +16,7 @@
 #include "smpc_cent6_kernels.h"
 #include "smpc_cent_split.h"
 #include "smpc_engine.h"
+#include "smpc_frontend_rt.h"
 
 namespace smpc
 {
@@ -52,6 +53,27 @@ namespace smpc
   {
     static constexpr bool value = true;
   };
+  // what the engine keeps for its state front end: the device model of a compile-time stage-kernel family, or nothing for the run-time
+  // joint tree (RtDims: the table is CentEngine::rt_model, nq / nv are members)
+  template <class DK>
+  struct CentFront
+  {
+    static constexpr bool RT = false;
+    static constexpr int NJ = DK::NJ;
+    typedef Buffers<DK> Model; // only .model is used
+    typedef DevModel<DK> HostModel;
+  };
+  template <>
+  struct CentFront<RtDims>
+  {
+    static constexpr bool RT = true;
+    static constexpr int NJ = 0;
+    struct Model
+    {
+      void * model = nullptr;
+    };
+    typedef RtDevModel HostModel;
+  };
   // buffers of the dense path (6-D feet); empty for point feet
   template <class DC, int FS>
   struct Cent6Extra
@@ -64,7 +86,8 @@ namespace smpc
     double *parts0 = nullptr, *partsT = nullptr, *xdotT = nullptr; // (Cent6Args, smpc_cent6_kernels.h)
   };
 
-  // DK: Dims of the multibody robot (front-end FK; a FullDims selects the front end of the dense stage kernels), DC: CentDims
+  // DK: Dims of the multibody robot (front-end FK; a FullDims selects the front end of the dense stage kernels; RtDims: the front end on the
+  // run-time joint tree, smpc_frontend_rt.h -- any robot table with DC's feet), DC: CentDims
   template <class DK, class DC>
   class CentEngine : public MpcEngineBase
   {
@@ -83,7 +106,11 @@ namespace smpc
     std::vector<stream_t> part_stream; // [nparts - 1] (part 0 runs on `stream`)
     std::vector<event_t> part_event;   // [nparts - 1] completion of a part, [nparts] stagger events
     event_t ev_fork{};
-    Buffers<DK> fk; // only .model is used (front-end kernel)
+    static constexpr bool RT = CentFront<DK>::RT;
+    typename CentFront<DK>::Model fk; // only .model is used (front-end kernel)
+    RtDevModel * rt_model = nullptr;  // the robot table of frontend_rt_body: the front end of an RtDims engine; on the others allocated by the first debug_frontend_rt
+    smpc_robot_model robot;           // (host copy: the source of rt_model)
+    int nq_mb = 0, nv_mb = 0, nx_mb = 0; // sizes of the measured multibody state
     std::vector<CentStage<DC>> horizon, cycle;
     CentStage<DC> standing;
     double com_ref_member[3] = {0, 0, 0}; // CentroidalOCP::com_ref_ (last setPoseBase)
@@ -100,7 +127,7 @@ namespace smpc
         throw std::runtime_error("batch must be positive");
       if (cs.force_size != DC::FS)
         throw std::runtime_error("force size in settings does not match reference force size");
-      if (rm->nfeet != DC::NF || rm->njoints != DK::NJ)
+      if (rm->nfeet != DC::NF || (!RT && rm->njoints != CentFront<DK>::NJ))
         throw std::runtime_error("robot shape (njoints, nfeet) does not match this kernel instantiation");
       if ((int)cs.w_u.size() != DC::NU * DC::NU || cs.w_com.size() != 9 || cs.w_linear_mom.size() != 9 || cs.w_angular_mom.size() != 9
           || cs.w_linear_acc.size() != 9 || cs.w_angular_acc.size() != 9)
@@ -111,16 +138,29 @@ namespace smpc
         throw std::runtime_error("centroidal OCP with 6-D feet: at most 255 stages");
       open_stream();
       force_size = DC::FS;
-      const int dd[8] = {DK::NQ, DK::NV, 9, 9, DC::NU, DC::NC, DC::NF, H}; // nq, nv of the robot; the problem state is [com; h_lin; h_ang]
+      robot = *rm;
+      nq_mb = rm->njoints + 6;
+      nv_mb = rm->njoints + 5;
+      nx_mb = nq_mb + nv_mb;
+      const int dd[8] = {nq_mb, nv_mb, 9, 9, DC::NU, DC::NC, DC::NF, H}; // nq, nv of the robot; the problem state is [com; h_lin; h_ang]
       std::copy(dd, dd + 8, dims);
       x_reference.assign(9, 0.0);
       mass = rm->total_mass;
       // ---- models ----
-      std::vector<DevModel<DK>> hk(1);
-      std::memset(&hk[0], 0, sizeof(DevModel<DK>));
-      fill_tree_model<DK>(rm, hk[0]);
-      fk.model = (DevModel<DK> *)dev_alloc(sizeof(DevModel<DK>));
-      h2d(fk.model, hk.data(), sizeof(DevModel<DK>), stream);
+      std::vector<typename CentFront<DK>::HostModel> hk(1);
+      if constexpr (RT)
+      {
+        fill_rt_model(rm, hk[0]);
+        rt_model = (RtDevModel *)dev_alloc(sizeof(RtDevModel));
+        h2d(rt_model, hk.data(), sizeof(RtDevModel), stream);
+      }
+      else
+      {
+        std::memset(&hk[0], 0, sizeof(DevModel<DK>));
+        fill_tree_model<DK>(rm, hk[0]);
+        fk.model = (DevModel<DK> *)dev_alloc(sizeof(DevModel<DK>));
+        h2d(fk.model, hk.data(), sizeof(DevModel<DK>), stream);
+      }
       std::vector<CentDevModel<DC>> hc(1);
       CentDevModel<DC> & m = hc[0];
       std::memset(&m, 0, sizeof(m));
@@ -213,13 +253,13 @@ namespace smpc
         buf.dbg = dalloc(64);
       buf.stages = (CentStage<DC> *)dev_alloc((size_t)H * sizeof(CentStage<DC>));
       buf.model = (CentDevModel<DC> *)dev_alloc(sizeof(CentDevModel<DC>));
-      X_dev = dalloc((size_t)B * DK::NX);
+      X_dev = dalloc((size_t)B * nx_mb);
       cstate_dev = dalloc((size_t)B * 9);
       feet_dev = dalloc((size_t)B * DC::NF * 3);
       h2d(buf.model, hc.data(), sizeof(CentDevModel<DC>), stream);
       stream_sync(stream);
-      x_model_ref.assign(DK::NX, 0.0);
-      for (int i = 0; i < DK::NQ; i++)
+      x_model_ref.assign(nx_mb, 0.0);
+      for (int i = 0; i < nq_mb; i++)
         x_model_ref[i] = rm->q_ref[i];
 
       // ---- default problem (OCPHandler::createProblem, src/ocp-handler.cpp:96-137): all feet in contact, identity
@@ -249,6 +289,7 @@ namespace smpc
       dev_free(buf.stages);
       dev_free(buf.model);
       dev_free(fk.model);
+      dev_free(rt_model);
       dev_free(cold.dev);
     }
 
@@ -260,17 +301,31 @@ namespace smpc
     {
       if (count < 0)
         count = B;
-      FrontendArgs<DK> fa;
-      fa.b = fk;
-      fa.X = Xd + (size_t)inst0 * DK::NX;
-      fa.feet = feet_dev + (size_t)inst0 * DC::NF * 3;
-      fa.com = nullptr;
-      fa.hg = nullptr;
-      fa.cstate = cstate_dev + (size_t)inst0 * 9;
-      if constexpr (cent_is_full_dims<DK>::value)
-        timed_launch<FrontendArgs<DK>, frontend_full_body<DK>, 64>(CKID_FRONTEND, count, fa, aux, on);
+      if constexpr (RT)
+      {
+        FrontendRtArgs fa;
+        fa.model = rt_model;
+        fa.X = Xd + (size_t)inst0 * nx_mb;
+        fa.feet = feet_dev + (size_t)inst0 * DC::NF * 3;
+        fa.com = nullptr;
+        fa.hg = nullptr;
+        fa.cstate = cstate_dev + (size_t)inst0 * 9;
+        timed_launch<FrontendRtArgs, frontend_rt_body, 64>(CKID_FRONTEND, count, fa, aux, on);
+      }
       else
-        timed_launch<FrontendArgs<DK>, frontend_body<DK>, 64>(CKID_FRONTEND, count, fa, aux, on);
+      {
+        FrontendArgs<DK> fa;
+        fa.b = fk;
+        fa.X = Xd + (size_t)inst0 * nx_mb;
+        fa.feet = feet_dev + (size_t)inst0 * DC::NF * 3;
+        fa.com = nullptr;
+        fa.hg = nullptr;
+        fa.cstate = cstate_dev + (size_t)inst0 * 9;
+        if constexpr (cent_is_full_dims<DK>::value)
+          timed_launch<FrontendArgs<DK>, frontend_full_body<DK>, 64>(CKID_FRONTEND, count, fa, aux, on);
+        else
+          timed_launch<FrontendArgs<DK>, frontend_body<DK>, 64>(CKID_FRONTEND, count, fa, aux, on);
+      }
     }
     // first instance / instance count of part p (whole wavefront groups of 64)
     void part_range(int p, int np, int & i0, int & n) const
@@ -390,7 +445,7 @@ namespace smpc
       a.reset_preg = 0;
       a.iters = 1;
       a.X = Xd;
-      a.nx_mb = DK::NX;
+      a.nx_mb = nx_mb;
       a.cstate = cstate_dev;
       a.feet = feet_dev;
       for (int f = 0; f < DC::NF; f++)
@@ -412,9 +467,9 @@ namespace smpc
     // reference state.  All B wavefronts run the same cold solve (it is identical work, and cheaper than a broadcast).
     void cold_solve(const CentStage<DC> & def)
     {
-      std::vector<double> X((size_t)B * DK::NX);
+      std::vector<double> X((size_t)B * nx_mb);
       for (int b = 0; b < B; b++)
-        std::copy(x_model_ref.begin(), x_model_ref.end(), X.begin() + (size_t)b * DK::NX);
+        std::copy(x_model_ref.begin(), x_model_ref.end(), X.begin() + (size_t)b * nx_mb);
       h2d(X_dev, X.data(), X.size() * sizeof(double), stream);
       launch_frontend(X_dev, true);
       std::vector<double> cst((size_t)B * 9), feet((size_t)B * DC::NF * 3);
@@ -622,18 +677,57 @@ namespace smpc
     {
       const size_t nf = (size_t)B * DC::NF * 3, nc = (size_t)B * 3, nh = (size_t)B * 6, ns = (size_t)B * 9;
       double * st = staging((nf + nc + nh + ns) * sizeof(double));
-      h2d(X_dev, X, (size_t)B * DK::NX * sizeof(double), stream);
-      FrontendArgs<DK> fa;
-      fa.b = fk;
-      fa.X = X_dev;
-      fa.feet = st;
-      fa.com = st + nf;
-      fa.hg = st + nf + nc;
-      fa.cstate = st + nf + nc + nh;
-      if constexpr (cent_is_full_dims<DK>::value)
-        launch<FrontendArgs<DK>, frontend_full_body<DK>, 64, 1, 1>(B, stream, fa);
+      h2d(X_dev, X, (size_t)B * nx_mb * sizeof(double), stream);
+      if constexpr (RT)
+        launch_rt_aux(st, st + nf, st + nf + nc, st + nf + nc + nh);
       else
-        launch<FrontendArgs<DK>, frontend_body<DK>, 64, 1, 1>(B, stream, fa);
+      {
+        FrontendArgs<DK> fa;
+        fa.b = fk;
+        fa.X = X_dev;
+        fa.feet = st;
+        fa.com = st + nf;
+        fa.hg = st + nf + nc;
+        fa.cstate = st + nf + nc + nh;
+        if constexpr (cent_is_full_dims<DK>::value)
+          launch<FrontendArgs<DK>, frontend_full_body<DK>, 64, 1, 1>(B, stream, fa);
+        else
+          launch<FrontendArgs<DK>, frontend_body<DK>, 64, 1, 1>(B, stream, fa);
+      }
+      read_front(st, nf, nc, nh, ns, feet, com, hg, cstate);
+    }
+    // frontend_rt_body on X_dev (auxiliary kernel symbol: not a launch of the control loop)
+    void launch_rt_aux(double * feet, double * com, double * hg, double * cstate)
+    {
+      FrontendRtArgs fa;
+      fa.model = rt_model;
+      fa.X = X_dev;
+      fa.feet = feet;
+      fa.com = com;
+      fa.hg = hg;
+      fa.cstate = cstate;
+      launch<FrontendRtArgs, frontend_rt_body, 64, 1, 1>(B, stream, fa);
+    }
+    // smpc_debug_frontend_rt: update_internal_data through the front end on the run-time joint tree, whatever front end the handle uses
+    void debug_frontend_rt(const double * X, double * feet, double * com, double * hg, double * cstate) override
+    {
+      set_device(device_id);
+      if (!rt_model)
+      {
+        RtDevModel hrt;
+        fill_rt_model(&robot, hrt);
+        rt_model = (RtDevModel *)dev_alloc(sizeof(RtDevModel));
+        h2d(rt_model, &hrt, sizeof(RtDevModel), stream);
+        stream_sync(stream);
+      }
+      const size_t nf = (size_t)B * DC::NF * 3, nc = (size_t)B * 3, nh = (size_t)B * 6, ns = (size_t)B * 9;
+      double * st = staging((nf + nc + nh + ns) * sizeof(double));
+      h2d(X_dev, X, (size_t)B * nx_mb * sizeof(double), stream);
+      launch_rt_aux(st, st + nf, st + nf + nc, st + nf + nc + nh);
+      read_front(st, nf, nc, nh, ns, feet, com, hg, cstate);
+    }
+    void read_front(const double * st, size_t nf, size_t nc, size_t nh, size_t ns, double * feet, double * com, double * hg, double * cstate)
+    {
       if (feet)
         d2h(feet, st, nf * sizeof(double), stream);
       if (com)
@@ -689,7 +783,7 @@ namespace smpc
       double * st = staging((2 * n9 + 2 * nu) * sizeof(double));
       if (X_meas)
       {
-        h2d(X_dev, X_meas, (size_t)B * DK::NX * sizeof(double), stream);
+        h2d(X_dev, X_meas, (size_t)B * nx_mb * sizeof(double), stream);
         launch_frontend(X_dev, true);
       }
       CentInterpArgs<DC> ia;
@@ -723,6 +817,8 @@ namespace smpc
       io.tag(B, "batch");
       io.tag(H, "horizon");
       io.tag(DC::NU, "nu");
+      if constexpr (RT)
+        io.tag(nq_mb, "nq of the robot"); // (the built shapes follow from nu)
       io.pod(head);
       io.pod(walking);
       io.host(velocity_base, sizeof(velocity_base));
@@ -750,7 +846,7 @@ namespace smpc
     void iterate_host(const double * X) override
     {
       set_device(device_id);
-      h2d(X_dev, X, (size_t)B * DK::NX * sizeof(double), stream);
+      h2d(X_dev, X, (size_t)B * nx_mb * sizeof(double), stream);
       iterate_device(X_dev);
       stream_sync(stream);
     }

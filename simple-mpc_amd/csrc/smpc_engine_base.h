@@ -554,6 +554,10 @@ namespace smpc
     virtual void debug_lq(int, int, double *) { throw InvalidCall(KINO_ONLY); }
     virtual void debug_terminal(int, double *, double *) { throw InvalidCall(KINO_ONLY); }
     virtual void phase_cycles(double * out64) = 0;
+    virtual void debug_frontend_rt(const double *, double *, double *, double *, double *)
+    {
+      throw InvalidCall("smpc_debug_frontend_rt needs a centroidal handle (smpc_create_centroidal)");
+    }
     virtual void full_forward_dynamics(int, const double *, const double *, const unsigned *, const double *, const double *, double, double, int, double *,
                                        double *, int *, double *)
     {

@@ -15,9 +15,9 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import IdSettingsC, CentroidalSettingsC, FullDynamicsSettingsC, KinodynamicsSettingsC, MpcSettingsC, SmpcLib, default_lib
+from ._capi import IdSettingsC, CentroidalSettingsC, FullDynamicsSettingsC, KinodynamicsSettingsC, MpcSettingsC, RobotModelC, SmpcLib, default_lib
 
-__all__ = ["load_robot", "RobotModelHandler", "RobotDataHandler", "KinodynamicsOCP", "CentroidalOCP", "FullDynamicsOCP", "MPC", "BatchedMPC", "Interpolator", "FrictionCompensation", "KinodynamicsID", "CentroidalID", "centroidal_dynamics"]
+__all__ = ["load_robot", "robot_from_table", "RobotModelC", "RobotModelHandler", "RobotDataHandler", "KinodynamicsOCP", "CentroidalOCP", "FullDynamicsOCP", "MPC", "BatchedMPC", "Interpolator", "FrictionCompensation", "KinodynamicsID", "CentroidalID", "centroidal_dynamics"]
 
 
 def load_robot(name, lib=None):
@@ -27,6 +27,17 @@ def load_robot(name, lib=None):
     if not ptr:
         raise RuntimeError("unknown robot %r" % name)
     return ptr
+
+
+def robot_from_table(table):
+    """A caller-filled robot table (RobotModelC, the mirror of smpc_robot_model in include/smpc_robot.h; or a pointer to one, as load_robot
+    returns) as a model for RobotModelHandler: stands in for a pinocchio.Model built by the caller.  The table is copied.  Centroidal
+    problems take any table with 4 point feet or 2 flat feet and up to 32 joints (the library validates it when the MPC is built); the
+    other problems are built for the shapes of the built-in robots."""
+    src = table.contents if hasattr(table, "contents") else table
+    if not isinstance(src, RobotModelC):
+        raise TypeError("robot_from_table takes a RobotModelC")
+    return C.pointer(RobotModelC.from_buffer_copy(src))  # (the pointer keeps its copy alive)
 
 
 class RobotModelHandler:
@@ -938,6 +949,17 @@ class BatchedMPC:
         hg, cs = np.zeros((self.B, 6)), np.zeros((self.B, 9))
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         self._lib.check(self._lib.L.smpc_update_internal_data(self._h, X, p(feet), p(com), p(hg), p(cs)))
+        return dict(feet=feet, com=com, hg=hg, centroidal_state=cs)
+
+    def debugFrontendRt(self, X):
+        """(tests) updateInternalData computed by the front end on the run-time joint tree, on the robot table of any centroidal handle."""
+        X = np.ascontiguousarray(np.array(X, dtype=np.float64))
+        if X.shape != (self.B, self.nx_in):
+            raise RuntimeError("X must have shape (batch, nq + nv)")
+        feet, com = np.zeros((self.B, self.nf, 3)), np.zeros((self.B, 3))
+        hg, cs = np.zeros((self.B, 6)), np.zeros((self.B, 9))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._lib.check(self._lib.L.smpc_debug_frontend_rt(self._h, X, p(feet), p(com), p(hg), p(cs)))
         return dict(feet=feet, com=com, hg=hg, centroidal_state=cs)
 
     def constraintDynamics(self, X, tau, contact_mask, Kp=None, Kd=None, prox_accuracy=0.0, prox_mu=0.0, prox_max_iter=0):

@@ -1,0 +1,155 @@
+// Stand-alone host program for the validation of caller-filled robot tables (simple-mpc_amd/csrc/smpc_robot_check.h), which runs before a
+// centroidal engine with a run-time joint tree allocates anything.  Built with -fsanitize=address,undefined by
+// tests/test_robot_table_host.py; every table lives in a heap block of exactly sizeof(smpc_robot_model) bytes, so that a read past the
+// struct -- a table that claims 33 joints, a foot on joint 1000 -- is a sanitizer report and not a silent pass.
+#include "smpc_robot_check.h"
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <string>
+
+static int failures = 0;
+#define CHECK(cond)                                                                                                    \
+  do                                                                                                                   \
+  {                                                                                                                    \
+    if (!(cond))                                                                                                       \
+    {                                                                                                                  \
+      std::printf("FAILED line %d: %s\n", __LINE__, #cond);                                                            \
+      failures++;                                                                                                      \
+    }                                                                                                                  \
+  } while (0)
+
+// a tree of nj joints: joint j hangs on (j - 1) / 3 (every inner joint has three children), axes cycle X / Y / Z, nf feet on the last joints
+static smpc_robot_model * make(int nj, int nf)
+{
+  smpc_robot_model * m = (smpc_robot_model *)std::malloc(sizeof(smpc_robot_model));
+  std::memset(m, 0, sizeof(*m));
+  std::snprintf(m->name, sizeof(m->name), "tree%d", nj);
+  m->njoints = nj;
+  m->nq = nj + 6;
+  m->nv = nj + 5;
+  double total = 0.0;
+  for (int j = 0; j < nj; j++)
+  {
+    m->parent[j] = j == 0 ? -1 : (j - 1) / 3;
+    m->jtype[j] = j == 0 ? 0 : 1 + j % 3;
+    m->jp_R[j][0] = m->jp_R[j][4] = m->jp_R[j][8] = 1.0;
+    m->jp_p[j][2] = -0.1;
+    m->mass[j] = 0.5 + 0.1 * j;
+    m->com[j][0] = 0.01;
+    m->inertia[j][0] = m->inertia[j][2] = m->inertia[j][5] = 0.01;
+    total += m->mass[j];
+  }
+  m->nfeet = nf;
+  for (int f = 0; f < nf; f++)
+  {
+    std::snprintf(m->foot_name[f], sizeof(m->foot_name[f]), "foot%d", f);
+    m->foot_joint[f] = nj - nf + f;
+    m->foot_p[f][2] = -0.05;
+    m->foot_ref_p[f][2] = -0.4;
+  }
+  m->q_ref[2] = 0.5;
+  m->q_ref[6] = 1.0;
+  for (int j = 0; j + 1 < nj; j++)
+  {
+    m->q_lo[j] = -1.0;
+    m->q_hi[j] = 1.0;
+  }
+  m->total_mass = total;
+  return m;
+}
+
+template <class F>
+static void refused(int nj, int nf, F && edit, const char * field)
+{
+  smpc_robot_model * m = make(nj, nf);
+  edit(*m);
+  const std::string why = smpc::robot_table_error(m);
+  if (why.rfind("robot table: ", 0) != 0 || why.find(field) == std::string::npos)
+  {
+    std::printf("FAILED: expected a refusal that names %s, got \"%s\"\n", field, why.c_str());
+    failures++;
+  }
+  std::free(m);
+}
+
+int main()
+{
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  // good tables: the smallest, the shapes of the tests, the bound
+  for (int nj : {2, 13, 14, 19, 31, SMPC_MAX_JOINTS})
+    for (int nf : {1, 2, 4})
+    {
+      if (nf > nj)
+        continue;
+      smpc_robot_model * m = make(nj, nf);
+      const std::string why = smpc::robot_table_error(m);
+      if (!why.empty())
+      {
+        std::printf("FAILED: good table (%d joints, %d feet) refused: %s\n", nj, nf, why.c_str());
+        failures++;
+      }
+      // total_mass inside / outside 1e-9 relative
+      const double tm = m->total_mass;
+      m->total_mass = tm * (1.0 + 5e-10);
+      CHECK(smpc::robot_table_error(m).empty());
+      m->total_mass = tm * (1.0 + 5e-9);
+      CHECK(smpc::robot_table_error(m).find("total_mass") != std::string::npos);
+      std::free(m);
+    }
+  // joint counts the table cannot hold: nothing past the struct is read
+  refused(19, 4, [](smpc_robot_model & m) { m.njoints = SMPC_MAX_JOINTS + 1; m.nq = m.njoints + 6; m.nv = m.njoints + 5; }, "njoints");
+  refused(19, 4, [](smpc_robot_model & m) { m.njoints = 2147483647; }, "njoints");
+  refused(19, 4, [](smpc_robot_model & m) { m.njoints = 1; }, "njoints");
+  refused(19, 4, [](smpc_robot_model & m) { m.njoints = -5; }, "njoints");
+  refused(19, 4, [](smpc_robot_model & m) { m.nq += 1; }, "nq");
+  refused(19, 4, [](smpc_robot_model & m) { m.nv -= 1; }, "nv");
+  // tree
+  refused(19, 4, [](smpc_robot_model & m) { m.parent[0] = 0; }, "parent[0]");
+  refused(19, 4, [](smpc_robot_model & m) { m.parent[5] = 7; }, "parent[5]");
+  refused(19, 4, [](smpc_robot_model & m) { m.parent[5] = 5; }, "parent[5]");
+  refused(19, 4, [](smpc_robot_model & m) { m.parent[18] = -1; }, "parent[18]");
+  refused(32, 2, [](smpc_robot_model & m) { m.parent[31] = 1000000; }, "parent[31]");
+  refused(19, 4, [](smpc_robot_model & m) { m.jtype[0] = 1; }, "jtype[0]");
+  refused(19, 4, [](smpc_robot_model & m) { m.jtype[3] = 0; }, "jtype[3]");
+  refused(19, 4, [](smpc_robot_model & m) { m.jtype[18] = 4; }, "jtype[18]");
+  // numbers
+  refused(19, 4, [&](smpc_robot_model & m) { m.mass[14] = nan; }, "mass[14]");
+  refused(19, 4, [&](smpc_robot_model & m) { m.mass[0] = 0.0; }, "mass[0]");
+  refused(19, 4, [&](smpc_robot_model & m) { m.mass[2] = -1.0; }, "mass[2]");
+  refused(19, 4, [&](smpc_robot_model & m) { m.mass[2] = inf; }, "mass[2]");
+  refused(19, 4, [&](smpc_robot_model & m) { m.jp_R[4][8] = nan; }, "jp_R[4]");
+  refused(19, 4, [&](smpc_robot_model & m) { m.jp_p[18][0] = inf; }, "jp_p[18]");
+  refused(19, 4, [&](smpc_robot_model & m) { m.com[1][1] = -inf; }, "com[1]");
+  refused(19, 4, [&](smpc_robot_model & m) { m.inertia[9][5] = nan; }, "inertia[9]");
+  refused(19, 4, [&](smpc_robot_model & m) { m.foot_p[3][2] = nan; }, "foot_p[3]");
+  refused(19, 4, [&](smpc_robot_model & m) { m.foot_ref_p[0][0] = nan; }, "foot_ref_p[0]");
+  refused(19, 4, [&](smpc_robot_model & m) { m.q_ref[24] = nan; }, "q_ref");
+  refused(19, 4, [&](smpc_robot_model & m) { m.q_lo[17] = nan; }, "q_lo");
+  refused(19, 4, [&](smpc_robot_model & m) { m.q_hi[0] = inf; }, "q_hi");
+  refused(19, 4, [&](smpc_robot_model & m) { m.total_mass = nan; }, "total_mass");
+  refused(19, 4, [&](smpc_robot_model & m) { m.total_mass *= 0.5; }, "total_mass");
+  // feet
+  refused(19, 4, [](smpc_robot_model & m) { m.foot_joint[2] = 19; }, "foot_joint[2]");
+  refused(19, 4, [](smpc_robot_model & m) { m.foot_joint[0] = -1; }, "foot_joint[0]");
+  refused(19, 4, [](smpc_robot_model & m) { m.foot_joint[3] = 1000; }, "foot_joint[3]");
+  refused(19, 4, [](smpc_robot_model & m) { m.nfeet = SMPC_MAX_FEET + 1; }, "nfeet");
+  refused(19, 4, [](smpc_robot_model & m) { m.nfeet = 0; }, "nfeet");
+  // what lies past the table's own joints / feet is not looked at
+  {
+    smpc_robot_model * m = make(14, 2);
+    for (int j = 14; j < SMPC_MAX_JOINTS; j++)
+    {
+      m->parent[j] = 99;
+      m->jtype[j] = -3;
+      m->mass[j] = nan;
+    }
+    m->foot_joint[2] = m->foot_joint[3] = -7;
+    CHECK(smpc::robot_table_error(m).empty());
+    std::free(m);
+  }
+  if (failures == 0)
+    std::printf("robot table check: OK\n");
+  return failures == 0 ? 0 : 1;
+}

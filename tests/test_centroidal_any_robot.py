@@ -1,0 +1,342 @@
+"""Centroidal MPC for any robot table: the state front end on a run-time joint tree (simple-mpc_amd/csrc/smpc_frontend_rt.h) and the
+centroidal engines built on it, on three caller-filled tables (tests/robot_tables.py: quad_arm 19 joints / 4 point feet, biped_legs 13
+joints / 2 flat feet, tree32 32 joints / 2 flat feet) against the oracle, whose rigid-body code is run-time sized and reads the same struct.
+
+CPU tier: the kernel bodies compiled with the sequential-lane test backend (tests/emu); tests/test_centroidal_any_robot_gpu.py runs the
+same cases on the HIP library.
+
+Bars.  Front end: those of tests/test_frontend.py for handles other than the Go2 kinodynamics one (feet 1e-12, com 1e-13, hg and the
+centroidal state 1e-11, absolute).  Closed loop: tests/test_centroidal_mpc.py for point feet (xs at tol, us and K0 at 10 tol, identical
+line-search steps), tests/test_talos_centroidal.py for flat feet (xs and K0 at tol, us at 10 tol, mpc_setup.alphas_agree); tol = 1e-9 for
+the emulated kernels and 1e-4 on the device, as there.  The oracle alone, run twice on these robots and seeds, reproduces itself bit for
+bit (checked when the seeds were fixed)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import mpc_setup as S
+import oracle_lib as O
+import robot_tables as RT
+import simple_mpc
+from simple_mpc import _capi, _hostmath
+
+ROBOTS = ["quad_arm", "biped_legs", "tree32"]
+BAR = dict(feet=1e-12, com=1e-13, hg=1e-11, centroidal_state=1e-11)
+REFUSAL = r"robot shape \(njoints, nfeet, force_size\) does not match a built kernel instantiation"
+_INVALID = -1  # SMPC_ERR_INVALID (include/smpc.h)
+
+
+# ------------------------------------------------------------------------------------------------------------------ cases (lib = None: HIP)
+def frontend_vs_oracle(name, lib, B=8):
+    tab = RT.table(name)
+    gm, rb, _, _ = RT.make_product(tab, B, lib=lib)
+    X = RT.random_states(tab, B, seed=11)
+    ref = [rb.centroidal(x) for x in X]
+    want = dict(feet=np.stack([c["feet"] for c in ref]), com=np.stack([c["com"] for c in ref]), hg=np.stack([c["hg"] for c in ref]))
+    want["centroidal_state"] = np.concatenate([want["com"], want["hg"]], 1)
+    assert np.abs(want["hg"]).min(1).max() > 1e-3 and np.abs(X[:, 3:6]).max() > 0.05  # moving robots, tilted bases
+    worst = {}
+    for what, out in (("update_internal_data", gm.updateInternalData(X)), ("debug_frontend_rt", gm.debugFrontendRt(X))):
+        for k, bar in BAR.items():
+            worst[what, k] = float(np.abs(out[k] - want[k]).max())
+    print(name, {"%s %s" % k: "%.2e" % v for k, v in worst.items()})
+    for (what, k), v in worst.items():
+        assert v < BAR[k], (name, what, k, v)
+    # the host-side answers of the Python mirror on the same table (RobotDataHandler: getCentroidalState, getFootPose)
+    dh = simple_mpc.RobotDataHandler(gm.ocp_handler.model_handler)
+    for b in range(2):
+        dh.updateInternalData(X[b])
+        assert np.abs(dh.getCentroidalState() - want["centroidal_state"][b]).max() < BAR["hg"]
+        for f in range(rb.nf):
+            assert np.abs(dh.getFootPose(f).translation - want["feet"][b, f]).max() < BAR["feet"]
+    # a robot at rest has no momentum
+    rest = gm.updateInternalData(np.tile(rb.x_ref, (B, 1)))
+    assert np.abs(rest["hg"]).max() < 1e-13
+
+
+def rt_vs_templated(name, lib, B=8):
+    """frontend_rt_body against frontend_body<Go2> / frontend_full_body<Talos> on the robot of a built shape (same bars; the summation
+    order differs, so no bitwise statement)."""
+    maker = S.make_cent_product if name == "go2_like" else S.make_talos_cent_product
+    gm, rb, _, _ = maker(B, lib=lib, horizon=10)
+    X = RT.random_states(RT.table(name), B, seed=12)
+    a, b = gm.updateInternalData(X), gm.debugFrontendRt(X)
+    diff = {k: float(np.abs(a[k] - b[k]).max()) for k in BAR}
+    print("run-time front end vs templated front end,", name, {k: "%.2e" % v for k, v in diff.items()})
+    for k, v in diff.items():
+        assert v < BAR[k], (name, k, v)
+    ref = rb.centroidal(X[0])
+    assert np.abs(b["hg"][0] - ref["hg"]).max() < BAR["hg"] and np.abs(b["feet"][0] - ref["feet"]).max() < BAR["feet"]
+
+
+def closed_loop(name, lib, iters, tol, B=3):
+    om, gm, rb = RT.make_pair(RT.table(name), B, iters, lib=lib)
+    point = rb.nf == 4
+    assert len(om.cold_trace()) == len(gm.cold_trace())
+    assert S.rel_err(om.xs, gm.xs) < tol
+    masks, worst = set(), 0.0
+    for step in range(6):
+        X = RT.near_reference_states(rb, B, seed=step)
+        om.iterate(X)
+        gm.iterate(X)
+        e = dict(xs=S.rel_err(om.xs, gm.xs), us=S.rel_err(om.us, gm.us), K0=S.rel_err(om.K0, gm.K0))
+        print(name, "k=%d step %d" % (iters, step), {k: "%.2e" % v for k, v in e.items()}, "alpha", om.info[:, 2], gm.info[:, 2])
+        worst = max(worst, e["xs"])
+        assert e["xs"] < tol and e["us"] < 10 * tol, (step, e)
+        if point:
+            assert e["K0"] < 10 * tol, (step, e)
+            assert np.array_equal(om.info[:, 2], gm.info[:, 2]), "line-search step sizes differ"
+        else:
+            assert e["K0"] < tol, (step, e)
+            assert S.alphas_agree(om, gm), ("line-search step sizes differ", om.info[:, :4], gm.info[:, :4])
+        assert S.rel_err(om.foot_refs, gm.getReferencePoses()) < 1e-12
+        masks.add(tuple(gm.ocp_handler.getContactState(gm.H - 1)))
+    assert len(masks) >= 3, "a take-off and a touch-down must have entered the horizon"
+    return worst
+
+
+def independence(name, lib):
+    """B = 65 against handles of B = 64 and B = 1 holding the same instances (one wavefront per instance: block indices past 64)."""
+    tab = RT.table(name)
+    hs = []
+    for B in (65, 64, 1):
+        gm, rb, _, _ = RT.make_product(tab, B, 1, lib=lib)
+        gm.generateCycleHorizon(RT.cycle(rb.nf))
+        gm.switchToWalk(np.array([0.2, 0, 0, 0, 0, 0.1]))
+        hs.append(gm)
+    for step in range(2):
+        X = RT.near_reference_states(rb, 65, seed=40 + step)
+        for gm, rows in zip(hs, (slice(0, 65), slice(0, 64), slice(64, 65))):
+            gm.iterate(X[rows])
+    for n in ("xs", "us"):
+        a = getattr(hs[0], n)
+        assert np.array_equal(a[:64], getattr(hs[1], n)) and np.array_equal(a[64:], getattr(hs[2], n)), n
+    assert np.abs(hs[0].xs[0] - hs[0].xs[64]).max() > 1e-6
+
+
+def _walking(name, lib, B=3):
+    gm, rb, _, _ = RT.make_product(RT.table(name), B, 1, lib=lib)
+    gm.generateCycleHorizon(RT.cycle(rb.nf))
+    gm.switchToWalk(np.array([0.2, 0, 0, 0, 0, 0.1]))
+    return gm, rb
+
+
+def checkpoint_and_reset(name, lib):
+    a, rb = _walking(name, lib)
+    b, _ = _walking(name, lib)
+    X = [RT.near_reference_states(rb, 3, seed=60 + k) for k in range(5)]
+    for k in range(2):
+        a.iterate(X[k])
+    blob = a.save_state()
+    b.load_state(blob)
+    assert b.save_state() == blob
+    for k in range(2, 4):
+        a.iterate(X[k])
+        b.iterate(X[k])
+        for n in ("xs", "us", "vs", "lams", "K0", "info"):
+            assert np.array_equal(getattr(a, n), getattr(b, n)), (k, n)
+    # a checkpoint of another robot with the same problem sizes is refused
+    other = "biped_legs" if name == "tree32" else ("tree32" if name == "biped_legs" else None)
+    if other:
+        c, _ = _walking(other, lib)
+        with pytest.raises(RuntimeError, match="does not match"):
+            c.load_state(blob)
+    # standing (the stage list is the constructor's): a reset instance that iterates once is the instance of a fresh handle
+    a = RT.make_product(RT.table(name), 3, 1, lib=lib)[0]
+    c = RT.make_product(RT.table(name), 3, 1, lib=lib)[0]
+    for m in (a, c):
+        m.generateCycleHorizon(RT.cycle(rb.nf))
+        m.switchToStand()
+    for k in range(4):
+        a.iterate(X[k])
+    a.resetInstances([1])
+    a.iterate(X[4])
+    c.iterate(X[4])
+    for n in ("xs", "us", "vs", "lams", "K0", "info"):
+        assert np.array_equal(getattr(a, n)[1], getattr(c, n)[1]), n
+    assert np.array_equal(a.getReferencePoses()[1], c.getReferencePoses()[1])
+    assert not np.array_equal(a.us[0], c.us[0])
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU tier
+@pytest.fixture(scope="module")
+def lib(built):
+    return S.emu_lib()
+
+
+@pytest.mark.parametrize("name", ROBOTS)
+def test_frontend_against_oracle(lib, name):
+    frontend_vs_oracle(name, lib)
+
+
+@pytest.mark.parametrize("name", ["go2_like", "talos_like"])
+def test_runtime_frontend_against_templated_frontends(lib, name):
+    rt_vs_templated(name, lib)
+
+
+@pytest.mark.parametrize("iters", [1, 3])
+@pytest.mark.parametrize("name", ROBOTS)
+def test_closed_loop_against_oracle(lib, name, iters):
+    closed_loop(name, lib, iters, 1e-9)
+
+
+def test_instances_are_independent(lib):
+    independence("quad_arm", lib)
+
+
+@pytest.mark.parametrize("name", ROBOTS)
+def test_checkpoint_and_reset(lib, name):
+    checkpoint_and_reset(name, lib)
+
+
+def test_python_and_dims(lib):
+    gm, rb, _, _ = RT.make_product(RT.table("quad_arm"), 2, lib=lib)
+    d = np.zeros(8, np.int32)
+    lib.L.smpc_get_dims(gm._h, d)
+    assert list(d) == [25, 24, 9, 9, 12, 8, 4, 10]
+    assert gm.nx_in == 49 and gm.xs.shape == (2, 11, 9) and gm.us.shape == (2, 10, 12)
+    mh = gm.ocp_handler.model_handler
+    assert mh.nq == 25 and mh.nv == 24 and mh.getMass() == pytest.approx(rb.mass, rel=1e-15) and mh.getReferenceState().shape == (49,)
+    with pytest.raises(TypeError):
+        simple_mpc.robot_from_table("quad_arm")
+    t = RT.table("quad_arm")
+    p = simple_mpc.robot_from_table(t)
+    p.contents.mass[3] = 5.0  # a copy: the caller's table is not touched
+    assert t.mass[3] != 5.0
+
+
+def _create(lib, tab, fs=None, batch=1):
+    """smpc_create_centroidal on a table, return code and message (the handle, if any, is destroyed)."""
+    rb = RT.oracle_robot(RT.table("quad_arm" if tab.nfeet == 4 else "biped_legs"))  # (settings sized by the feet alone)
+    s, ms = RT.settings(rb, 10, 1)
+    fs = fs or s["force_size"]
+    arrs = [np.ascontiguousarray(s[k], float) for k in ("w_u", "w_com", "w_linear_mom", "w_angular_mom", "w_linear_acc", "w_angular_acc")]
+    if tab.nfeet * fs != arrs[0].shape[0]:
+        arrs[0] = np.eye(max(1, tab.nfeet * fs)) * 1e-3
+    cs = _capi.CentroidalSettingsC()
+    cs.timestep = s["timestep"]
+    for k, a in zip(("w_u", "w_com", "w_linear_mom", "w_angular_mom", "w_linear_acc", "w_angular_acc"), arrs):
+        setattr(cs, k, a.ctypes.data)
+    for i in range(3):
+        cs.gravity[i] = float(s["gravity"][i])
+    cs.mu, cs.Lfoot, cs.Wfoot, cs.force_size = s["mu"], s["Lfoot"], s["Wfoot"], fs
+    m = _capi.MpcSettingsC()
+    for k in S.MPC_KEYS:
+        setattr(m, k, ms[k])
+    m.T = 10
+    h = C.c_void_p()
+    rc = lib.L.smpc_create_centroidal(C.pointer(tab), C.byref(cs), C.byref(m), batch, -9.81, 0, C.byref(h))
+    msg = lib.L.smpc_last_error().decode() if rc != 0 else ""
+    if rc == 0:
+        lib.L.smpc_destroy(h)
+    return rc, msg
+
+
+def _bad(name, edit):
+    t = _capi.RobotModelC.from_buffer_copy(RT.table(name))
+    edit(t)
+    return t
+
+
+def test_invalid_tables_are_refused_by_field(lib):
+    def set_(field, j, v):
+        def f(t):
+            if j is None:
+                setattr(t, field, v)
+            else:
+                getattr(t, field)[j] = v
+        return f
+
+    cases = [
+        ("quad_arm", set_("parent", 5, 7), r"parent\[5\]"),
+        ("quad_arm", set_("parent", 0, 0), r"parent\[0\]"),
+        ("quad_arm", set_("jtype", 3, 0), r"jtype\[3\]"),
+        ("biped_legs", set_("jtype", 0, 1), r"jtype\[0\]"),
+        ("quad_arm", set_("nq", None, 26), r"\bnq\b"),
+        ("tree32", set_("nv", None, 38), r"\bnv\b"),
+        ("quad_arm", set_("mass", 14, float("nan")), r"mass\[14\]"),
+        ("tree32", set_("mass", 31, -1.0), r"mass\[31\]"),
+        ("quad_arm", set_("total_mass", None, RT.table("quad_arm").total_mass * (1 + 1e-6)), r"total_mass"),
+        ("biped_legs", set_("foot_joint", 1, 13), r"foot_joint\[1\]"),
+        ("tree32", lambda t: t.com[20].__setitem__(1, float("inf")), r"com\[20\]"),
+        ("quad_arm", lambda t: t.jp_p[18].__setitem__(2, float("nan")), r"jp_p\[18\]"),
+    ]
+    for name, edit, pat in cases:
+        rc, msg = _create(lib, _bad(name, edit))
+        assert rc == _INVALID, (pat, rc, msg)
+        assert __import__("re").search(pat, msg) and msg.startswith("robot table: "), (pat, msg)
+    # the good tables pass, also at the bound of total_mass
+    rc, msg = _create(lib, _bad("tree32", set_("total_mass", None, RT.table("tree32").total_mass * (1 + 1e-10))))
+    assert rc == 0, msg
+
+
+def test_shapes_outside_the_run_time_engine(lib):
+    rc, msg = _create(lib, _bad("tree32", lambda t: (setattr(t, "njoints", 33), setattr(t, "nq", 39), setattr(t, "nv", 38))))
+    assert rc == _INVALID and "njoints" in msg
+    rc, msg = _create(lib, _bad("quad_arm", lambda t: (setattr(t, "njoints", 1), setattr(t, "nq", 7), setattr(t, "nv", 6))))
+    assert rc == _INVALID and "njoints" in msg
+    import re
+
+    rc, msg = _create(lib, _bad("quad_arm", lambda t: setattr(t, "nfeet", 3)))
+    assert rc == _INVALID and re.fullmatch(REFUSAL, msg), msg
+    rc, msg = _create(lib, RT.table("quad_arm"), fs=6)  # 4 feet with 6-D forces: no such kernel family
+    assert rc == _INVALID and re.fullmatch(REFUSAL, msg), msg
+    rc, msg = _create(lib, RT.table("biped_legs"), fs=3)
+    assert rc == _INVALID and re.fullmatch(REFUSAL, msg), msg
+
+
+def test_other_problems_keep_their_refusal(lib):
+    """Kinodynamics and full dynamics are shaped around the joint count: quad_arm is refused there with the texts of before."""
+    tab = RT.table("quad_arm")
+    nv, nu_k, na = tab.nv, tab.nv - 6 + 12, tab.nv - 6
+    keep = []
+
+    def arr(*shape, diag=None):
+        a = np.ascontiguousarray(np.eye(shape[0]) * diag if diag is not None else np.zeros(shape))
+        keep.append(a)
+        return a.ctypes.data
+
+    m = _capi.MpcSettingsC()
+    rb = RT.oracle_robot(tab)
+    for k, v in RT.settings(rb, 10, 1)[1].items():
+        if k in S.MPC_KEYS:
+            setattr(m, k, v)
+    m.T = 10
+    ks = _capi.KinodynamicsSettingsC()
+    ks.timestep, ks.mu, ks.Lfoot, ks.Wfoot, ks.force_size = 0.01, 0.8, 0.01, 0.01, 3
+    ks.w_x, ks.w_u, ks.w_frame, ks.w_cent, ks.w_centder = arr(2 * nv, diag=1.0), arr(nu_k, diag=1.0), arr(3, diag=1.0), arr(6, diag=1.0), arr(6, diag=1.0)
+    ks.qmin, ks.qmax = arr(na), arr(na)
+    ks.gravity[2] = -9.81
+    h = C.c_void_p()
+    rc = lib.L.smpc_create(C.pointer(tab), C.byref(ks), C.byref(m), 1, -9.81, 0, C.byref(h))
+    assert rc < 0 and "robot shape (njoints, nfeet) does not match this kernel instantiation" == lib.L.smpc_last_error().decode()
+    fs = _capi.FullDynamicsSettingsC()
+    fs.timestep, fs.mu, fs.Lfoot, fs.Wfoot, fs.force_size = 0.01, 0.8, 0.01, 0.01, 3
+    fs.w_x, fs.w_u, fs.w_cent, fs.w_forces, fs.w_frame = arr(2 * nv, diag=1.0), arr(na, diag=1.0), arr(6, diag=1.0), arr(3, diag=1.0), arr(3, diag=1.0)
+    fs.umin, fs.umax, fs.qmin, fs.qmax, fs.Kp_correction, fs.Kd_correction = arr(na), arr(na), arr(na), arr(na), arr(3), arr(3)
+    fs.gravity[2] = -9.81
+    rc = lib.L.smpc_create_fulldynamics(C.pointer(tab), C.byref(fs), C.byref(m), 1, -9.81, 0, C.byref(h))
+    assert rc < 0 and "robot shape (njoints, nfeet, force_size) does not match a built kernel instantiation" == lib.L.smpc_last_error().decode()
+
+
+def test_debug_frontend_needs_a_centroidal_handle(lib):
+    gm, rb, _, _ = S.make_product(1, lib=lib, horizon=10)
+    with pytest.raises(RuntimeError, match="smpc_debug_frontend_rt needs a centroidal handle"):
+        gm.debugFrontendRt(rb.x_ref[None, :])
+
+
+def test_example_on_the_cpu_build(built):
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = os.path.join(root, "examples", "quadruped_arm_centroidal_batched.py")
+    src = open(path).read()
+    assert "LIB = None" in src
+    code = "import sys; sys.path.insert(0, %r); sys.argv = ['x', '3', '2']; __file__ = %r\n" % (os.path.join(root, "tests"), path)
+    code += src.replace("LIB = None", "LIB = __import__('mpc_setup').emu_lib()")
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, SMPC_EXAMPLE_HORIZON="12"), cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert "3 quadrupeds with an arm (19 joints)" in p.stdout and "weight 186.6 N" in p.stdout
