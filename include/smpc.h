@@ -518,6 +518,21 @@ int smpc_sim_step_device(smpc_handle * h, double * X_device, const double * tau_
 /* (tests) intermediate results of the last solve, padded layouts of simple-mpc_amd/csrc/smpc_id.h: what = 0 M, 1 nle, 2 J, 3 dJ v, 4 foot
  * velocities, 5 H [32][32], 6 g [32], 7 C [80][32], 8 l [80], 9 u [80], 10 centre of mass [3], 11 foot positions [3 nfeet], 12 torques [nv - 6]; every one [B][...] */
 int smpc_id_debug_get(smpc_id_handle * h, int what, double * out);
+/* Any robot table with 4 point feet (force_size 3) and 2 .. SMPC_MAX_JOINTS joints (simple-mpc_amd/csrc/smpc_id_rt.h): the reference takes
+ * any pinocchio::Model in KinodynamicsID / CentroidalID (src/inverse-dynamics/kinodynamics-id.cpp:7-237, centroidal-id.cpp:6-147).
+ * smpc_id_create keeps its two built shapes (13 joints / 4 point feet, 23 joints / 2 flat feet) on their templated kernels; every other
+ * point-foot table is validated like the centroidal MPC's (SMPC_ERR_INVALID naming the field, nothing allocated) and served by kernels
+ * that read the joint tree at run time.  Flat feet on any other tree are refused.
+ *   smpc_id_get_dims        dims[10] = B, nq, nv, nfeet, force size of a target, n (variables), m (rows), n and m padded to 16, contact-
+ *                           motion rows per foot: what the buffers of this section are sized by (kinodynamics-id.cpp:24-38 reads them
+ *                           from the model)
+ *   smpc_debug_id_force_rt  (tests) on != 0: handles created from now on for the built point-foot shape use the run-time kernels too;
+ *                           returns the previous setting.  One process-wide atomic flag: a handle created by another thread while it is
+ *                           set takes the run-time kernels as well.
+ * The limit vectors of smpc_id_settings are raw pointers: the C ABI reads nv - 6 entries of each and cannot check their lengths; the
+ * Python and C++ mirrors, which hold the containers, refuse a vector of another length before they call smpc_id_create. */
+int smpc_id_get_dims(smpc_id_handle * h, int * dims);
+int smpc_debug_id_force_rt(int on);
 
 #ifdef __cplusplus
 }

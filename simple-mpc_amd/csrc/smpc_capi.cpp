@@ -6,7 +6,9 @@
 #include "smpc_cent_engine.h"
 #include "smpc_full_engine.h"
 #include "smpc_id.h"
+#include "smpc_id_rt.h"
 #include "smpc_robot_check.h"
+#include <atomic>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -954,7 +956,8 @@ extern "C"
     });
   }
 
-  // ---- whole-body inverse-dynamics QP (smpc_id.h) ----
+  // ---- whole-body inverse-dynamics QP (smpc_id.h, smpc_id_rt.h) ----
+  static std::atomic<int> g_id_force_rt{0}; // (process-wide; read once per smpc_id_create)
   int smpc_id_create(const smpc_robot_model * robot, const smpc_id_settings * c, int batch, int device_id, smpc_id_handle ** out)
   {
     if (!robot || !c || !out)
@@ -993,14 +996,20 @@ extern "C"
       return fail(SMPC_ERR_INVALID, "task gains must not be negative");
     if (!(c->kp_base >= 0.0 && c->kp_posture >= 0.0 && c->kp_contact >= 0.0))
       return fail(SMPC_ERR_INVALID, "task gains must not be negative");
+    const bool quad = c->force_size == 6;
+    if (c->force_size != 0 && c->force_size != 3 && c->force_size != 6)
+      return fail(SMPC_ERR_INVALID, "force size must be 3 (point feet) or 6 (flat feet)");
+    // the two built shapes keep their templated engines and kernel symbols; every other table with 4 point feet: the engine on the run-time
+    // joint tree (smpc_id_rt.h), on a table that is checked before anything is allocated for it
+    std::string why;
+    const IdRoute route = id_route(robot, quad, FullGo2::NJ, FullGo2::NF, FullTalos::NJ, FullTalos::NF, g_id_force_rt.load() != 0, why);
+    if (route == ID_ROUTE_REFUSED)
+      return fail(SMPC_ERR_INVALID, why);
     const int na = robot->nv - 6;
     hs.tau_max.assign(c->effort_limit, c->effort_limit + na);
     hs.v_max.assign(c->velocity_limit, c->velocity_limit + na);
     hs.q_min.assign(c->q_min, c->q_min + na);
     hs.q_max.assign(c->q_max, c->q_max + na);
-    const bool quad = c->force_size == 6;
-    if (c->force_size != 0 && c->force_size != 3 && c->force_size != 6)
-      return fail(SMPC_ERR_INVALID, "force size must be 3 (point feet) or 6 (flat feet)");
     if (quad)
     {
       if (!c->quad_contact_points)
@@ -1011,13 +1020,28 @@ extern "C"
 #if defined(SMPC_KINO_ONLY) && !defined(SMPC_WITH_ID) // (tools/variant_build.sh <name> -DSMPC_WITH_ID: the ID engines too)
       throw std::runtime_error("SMPC_KINO_ONLY experiment build");
 #endif
-      if (!quad && robot->njoints == FullGo2::NJ && robot->nfeet == FullGo2::NF)
+      if (route == ID_ROUTE_GO2)
         *out = reinterpret_cast<smpc_id_handle *>(static_cast<IdEngineBase *>(new IdEngine<FullGo2>(robot, hs, batch, device_id)));
-      else if (quad && robot->njoints == FullTalos::NJ && robot->nfeet == FullTalos::NF)
+      else if (route == ID_ROUTE_TALOS)
         *out = reinterpret_cast<smpc_id_handle *>(static_cast<IdEngineBase *>(new IdEngine<FullTalos>(robot, hs, batch, device_id)));
       else
-        throw std::runtime_error("the inverse-dynamics engine is instantiated for 13 joints / 4 point feet and for 23 joints / 2 flat feet");
+        *out = reinterpret_cast<smpc_id_handle *>(static_cast<IdEngineBase *>(new IdEngineRt(robot, hs, batch, device_id)));
     });
+  }
+  // debug: send the built point-foot shape (13 joints / 4 point feet) through the run-time engine too, so that the two can be compared
+  int smpc_debug_id_force_rt(int on)
+  {
+    return g_id_force_rt.exchange(on != 0 ? 1 : 0);
+  }
+  int smpc_id_get_dims(smpc_id_handle * h, int * dims)
+  {
+    if (!h || !dims)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    IdEngineBase * e = reinterpret_cast<IdEngineBase *>(h);
+    const int d[10] = {e->B, e->nq, e->nv, e->nf, e->nfw, e->n, e->m, e->np, e->mp, e->nmot};
+    for (int i = 0; i < 10; i++)
+      dims[i] = d[i];
+    return SMPC_OK;
   }
   void smpc_id_destroy(smpc_id_handle * h) { delete reinterpret_cast<IdEngineBase *>(h); }
   int smpc_id_set_target(smpc_id_handle * h, int instance, const double * q, const double * v, const double * a, const uint8_t * contact, const double * f)
