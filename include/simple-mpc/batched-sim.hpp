@@ -1,0 +1,111 @@
+// simple-mpc/batched-sim.hpp -- header-only C++ host mirror of the batched rigid-body simulator over the C ABI of smpc.h
+// (smpc_robot_sim_*): the constrained forward dynamics the reference's FullDynamicsOCP obtains from pinocchio::constraintDynamics
+// (src/fulldynamics.cpp:39,50-75,139) and a semi-implicit Euler step, for any validated robot table, `batch` robots per launch.  The handle
+// carries the robot and nothing else.  Eigen types replaced by std::vector<double>; errors are rethrown as std::runtime_error.
+#pragma once
+#include "../smpc.h"
+#include "batched-mpc.hpp"
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+namespace simple_mpc
+{
+  class BatchedRobotSim
+  {
+  public:
+    // force_size 3: point contacts (LOCAL frame), 1 .. 4 feet; 6: flat contacts (LOCAL_WORLD_ALIGNED), 1 .. 2 feet.  gravity: empty = (0, 0, -9.81)
+    BatchedRobotSim(const smpc_robot_model * robot, int force_size, int batch, const std::vector<double> & gravity = {}, int device_id = 0)
+    {
+      if (!gravity.empty() && gravity.size() != 3)
+        throw std::runtime_error("gravity: 3 entries expected");
+      check(smpc_robot_sim_create(robot, force_size, batch, gravity.empty() ? nullptr : gravity.data(), device_id, &h_));
+      int d[5];
+      check(smpc_robot_sim_get_dims(h_, d));
+      batch_ = d[0];
+      nq_ = d[1];
+      nv_ = d[2];
+      nf_ = d[3];
+      fs_ = d[4];
+    }
+    ~BatchedRobotSim()
+    {
+      if (h_)
+        smpc_robot_sim_destroy(h_);
+    }
+    BatchedRobotSim(const BatchedRobotSim &) = delete;
+    BatchedRobotSim & operator=(const BatchedRobotSim &) = delete;
+    int batch() const { return batch_; }
+    int nq() const { return nq_; }
+    int nv() const { return nv_; }
+    int nfeet() const { return nf_; }
+    int force_size() const { return fs_; }
+
+    // X [n][nq + nv], tau [n][nv - 6], contact_mask [n] (bit per foot), Kp / Kd: force_size entries or empty (= 0) ->
+    // a [n][nv], lambda [n][force_size nfeet] (feet in contact first, the rest 0), iters [n]; n need not be the batch
+    void forwardDynamics(const std::vector<double> & X, const std::vector<double> & tau, const std::vector<unsigned> & contact_mask, const std::vector<double> & Kp,
+                         const std::vector<double> & Kd, std::vector<double> & a, std::vector<double> & lambda, std::vector<int> & iters,
+                         double prox_accuracy = 0.0, double prox_mu = 0.0, int prox_max_iter = 0)
+    {
+      const size_t n = contact_mask.size();
+      if (n == 0 || X.size() != n * (size_t)(nq_ + nv_) || tau.size() != n * (size_t)(nv_ - 6))
+        throw std::runtime_error("X [n][nq + nv], tau [n][nv - 6], contact_mask [n] expected");
+      gains(Kp, Kd);
+      a.resize(n * nv_);
+      lambda.resize(n * (size_t)(fs_ * nf_));
+      iters.resize(n);
+      check(smpc_robot_sim_forward_dynamics(h_, (int)n, X.data(), tau.data(), contact_mask.data(), Kp.empty() ? nullptr : Kp.data(), Kd.empty() ? nullptr : Kd.data(),
+                                            prox_accuracy, prox_mu, prox_max_iter, a.data(), lambda.data(), iters.data()));
+    }
+    // one step of the batch, states [B][nq + nv] and torques [B][nv - 6] resident on the device, X updated in place; asynchronous on the
+    // handle's stream.  mask_device: [B] uint32 on the device (bit per foot), overrides contact_state when not null
+    void stepDevice(double * X_device, const double * tau_device, const std::vector<bool> & contact_state, double dt, const std::vector<double> & Kp = {},
+                    const std::vector<double> & Kd = {}, const uint32_t * mask_device = nullptr)
+    {
+      if (!(dt > 0.0))
+        throw std::runtime_error("dt must be positive");
+      if (!mask_device && (int)contact_state.size() != nf_)
+        throw std::runtime_error("contact_state must have one entry per foot");
+      gains(Kp, Kd);
+      std::vector<uint8_t> c(contact_state.size());
+      for (size_t i = 0; i < c.size(); i++)
+        c[i] = contact_state[i] ? 1 : 0;
+      check(smpc_robot_sim_step_device(h_, X_device, tau_device, (int)c.size() == nf_ ? c.data() : nullptr, mask_device, Kp.empty() ? nullptr : Kp.data(),
+                                       Kd.empty() ? nullptr : Kd.data(), dt));
+    }
+    // issue the simulator's work on the MPC's stream from now on (nullptr: back to its own)
+    void shareStream(BatchedMPC * mpc) { check(smpc_robot_sim_share_stream(h_, mpc ? mpc->handle() : nullptr)); }
+    void wait() { check(smpc_robot_sim_wait(h_)); }
+    void * stream() { return smpc_robot_sim_get_stream(h_); }
+    // accelerations [B][nv] / contact forces [B][force_size nfeet] of the last step (host copies; join the handle's stream)
+    std::vector<double> lastAccelerations()
+    {
+      std::vector<double> a((size_t)batch_ * nv_);
+      check(smpc_robot_sim_read_last(h_, a.data(), nullptr));
+      return a;
+    }
+    std::vector<double> lastForces()
+    {
+      std::vector<double> f((size_t)batch_ * fs_ * nf_);
+      check(smpc_robot_sim_read_last(h_, nullptr, f.data()));
+      return f;
+    }
+    // the same as device pointers owned by the handle
+    void lastDevicePointers(double ** a_device, double ** lambda_device) { check(smpc_robot_sim_get_last(h_, a_device, lambda_device)); }
+    smpc_robot_sim * handle() { return h_; }
+
+  private:
+    static void check(int rc)
+    {
+      if (rc < 0)
+        throw std::runtime_error(smpc_last_error());
+    }
+    void gains(const std::vector<double> & Kp, const std::vector<double> & Kd) const
+    {
+      if ((!Kp.empty() && (int)Kp.size() != fs_) || (!Kd.empty() && (int)Kd.size() != fs_))
+        throw std::runtime_error("Kp, Kd: force_size Baumgarte gains each (or empty)");
+    }
+    smpc_robot_sim * h_ = nullptr;
+    int batch_ = 0, nq_ = 0, nv_ = 0, nf_ = 0, fs_ = 0;
+  };
+} // namespace simple_mpc

@@ -534,6 +534,46 @@ int smpc_id_debug_get(smpc_id_handle * h, int what, double * out);
 int smpc_id_get_dims(smpc_id_handle * h, int * dims);
 int smpc_debug_id_force_rt(int on);
 
+/* ---- batched rigid-body simulator for any robot table (simple-mpc_amd/csrc/smpc_sim_rt.h) ----
+ * A stand-alone handle that carries a robot table and nothing else (no OCP, no MPC settings): the constrained forward dynamics of
+ * smpc_full_forward_dynamics and the simulator step of smpc_sim_step_device for ANY validated table of smpc_robot.h, on a joint tree that
+ * is read at run time.  One kernel launch per step (dynamics and integration together).
+ *   smpc_robot_sim_create    force_size 3: point contacts (CONTACT_3D, LOCAL), 1 .. SMPC_MAX_FEET feet; force_size 6: flat contacts
+ *                            (CONTACT_6D, LOCAL_WORLD_ALIGNED), 1 .. 2 feet, so that a robot has at most 12 contact rows; 2 <= njoints <=
+ *                            SMPC_MAX_JOINTS, batch >= 1; gravity NULL = (0, 0, -9.81).  The table is validated like the centroidal MPC's.
+ *                            Anything else: SMPC_ERR_INVALID with a message that names the field, *out = NULL, nothing allocated.  The
+ *                            built-in tables are accepted and run the same kernel.
+ *   smpc_robot_sim_get_dims  dims[5] = B, nq, nv, nfeet, force_size
+ *   smpc_robot_sim_share_stream      as smpc_id_share_stream: from now on the simulator issues its work on the MPC handle's stream (NULL:
+ *                            back to its own) -- MPC step, targets, QP solve and simulator step form one in-order queue.  The stream
+ *                            belongs to the MPC handle: go back (NULL) before that handle is destroyed.
+ *   smpc_robot_sim_forward_dynamics  host buffers, layouts and defaults of smpc_full_forward_dynamics: X [n][nq + nv], tau [n][nv - 6],
+ *                            contact_mask [n] (bit per foot), Kp / Kd [force_size] (NULL = 0), ProximalSettings(1e-9, 1e-10, 10) for
+ *                            arguments <= 0; a_out [n][nv], lambda_out [n][force_size nfeet] (forces ON the robot in the contact frame,
+ *                            feet in contact first, the rest exactly 0), iters_out [n] (may be NULL).  n need not be B.
+ *   smpc_robot_sim_step_device       constrained forward dynamics, then v <- v + a dt, q <- integrate(q, v dt) (semi-implicit Euler);
+ *                            X_device [B][nq + nv] is updated in place, tau_device [B][nv - 6].  contact: nfeet flags on the host, the same
+ *                            for every robot; mask_device [B] (device, bit per foot), when not NULL, overrides it with one mask per robot.
+ *                            Asynchronous on the handle's stream (smpc_robot_sim_wait joins).  dt <= 0: SMPC_ERR_INVALID.
+ *   smpc_robot_sim_get_last  accelerations [B][nv] and contact forces [B][force_size nfeet] of the last step (device pointers owned by the
+ *                            handle, written by the step on its stream): logging without a second solve.
+ *   smpc_robot_sim_read_last the same copied to host buffers a_out [B][nv], lambda_out [B][force_size nfeet] (either may be NULL); joins
+ *                            the handle's stream. */
+typedef struct smpc_robot_sim smpc_robot_sim;
+int smpc_robot_sim_create(const smpc_robot_model * robot, int force_size, int batch, const double * gravity, int device_id, smpc_robot_sim ** out);
+void smpc_robot_sim_destroy(smpc_robot_sim * sim);
+int smpc_robot_sim_get_dims(smpc_robot_sim * sim, int * dims);
+int smpc_robot_sim_wait(smpc_robot_sim * sim);
+void * smpc_robot_sim_get_stream(smpc_robot_sim * sim);
+int smpc_robot_sim_share_stream(smpc_robot_sim * sim, smpc_handle * mpc);
+int smpc_robot_sim_forward_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, const unsigned * contact_mask, const double * Kp,
+                                    const double * Kd, double prox_accuracy, double prox_mu, int prox_max_iter, double * a_out, double * lambda_out,
+                                    int * iters_out);
+int smpc_robot_sim_step_device(smpc_robot_sim * sim, double * X_device, const double * tau_device, const uint8_t * contact, const uint32_t * mask_device,
+                               const double * Kp, const double * Kd, double dt);
+int smpc_robot_sim_get_last(smpc_robot_sim * sim, double ** a_device, double ** lambda_device);
+int smpc_robot_sim_read_last(smpc_robot_sim * sim, double * a_out, double * lambda_out);
+
 #ifdef __cplusplus
 }
 #endif

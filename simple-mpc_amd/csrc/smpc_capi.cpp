@@ -7,6 +7,7 @@
 #include "smpc_full_engine.h"
 #include "smpc_id.h"
 #include "smpc_id_rt.h"
+#include "smpc_sim_rt.h"
 #include "smpc_robot_check.h"
 #include <atomic>
 #include <cstring>
@@ -27,6 +28,11 @@ typedef FullDims<13, 4, 3, 5, 4> FullGo2ConeLand; // force_cone and land_cstr: t
 typedef FullDims<23, 2, 6> FullTalos; // Talos-class humanoid: 22 joint torques, two 6-D feet with wrench cones
 typedef FullDims<23, 2, 6, 0, 6> FullTalosLand; // land_cstr: 6 frame-velocity rows per landing foot
 typedef FullDims<23, 2, 6, 0, 0, 1> KinoTalos;  // KINODYNAMICS OCP of the Talos-class biped: 6-D feet, wrench cones (KinodynamicsOCP with force_size 6)
+
+struct smpc_robot_sim // stand-alone simulator handle: a robot table and nothing else (smpc_sim_rt.h)
+{
+  std::unique_ptr<RobotSimRt> e;
+};
 
 struct smpc_handle
 {
@@ -1171,5 +1177,90 @@ extern "C"
     if (!h || !out)
       return fail(SMPC_ERR_INVALID, "null argument");
     return guarded([&] { reinterpret_cast<IdEngineBase *>(h)->debug_get(what, out); });
+  }
+
+  // ---- batched rigid-body simulator on a run-time joint tree (smpc_sim_rt.h) ----
+  int smpc_robot_sim_create(const smpc_robot_model * robot, int force_size, int batch, const double * gravity, int device_id, smpc_robot_sim ** out)
+  {
+    if (!robot || !out)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    *out = nullptr;
+    // admission before anything else: nothing is allocated for a table, a contact size or a batch the simulator is not built for
+    const std::string why = sim_rt_admission_error(robot, force_size, batch);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    if (gravity && !(std::isfinite(gravity[0]) && std::isfinite(gravity[1]) && std::isfinite(gravity[2])))
+      return fail(SMPC_ERR_INVALID, "gravity is not finite");
+    if (device_count() <= 0)
+      return fail(SMPC_ERR_NO_DEVICE, "no HIP device visible: the simulator has no CPU path");
+    return guarded([&] {
+      std::unique_ptr<smpc_robot_sim> h(new smpc_robot_sim());
+      h->e.reset(new RobotSimRt(robot, force_size, batch, gravity, device_id));
+      *out = h.release();
+    });
+  }
+  void smpc_robot_sim_destroy(smpc_robot_sim * sim) { delete sim; }
+  int smpc_robot_sim_get_dims(smpc_robot_sim * sim, int * dims)
+  {
+    if (!sim || !dims)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    const RobotSimRt & e = *sim->e;
+    const int d[5] = {e.B, e.sz.nq, e.sz.nv, e.sz.nfeet, e.sz.fs};
+    for (int i = 0; i < 5; i++)
+      dims[i] = d[i];
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_wait(smpc_robot_sim * sim)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { sim->e->wait(); });
+  }
+  void * smpc_robot_sim_get_stream(smpc_robot_sim * sim) { return sim ? stream_native(sim->e->stream) : nullptr; }
+  int smpc_robot_sim_share_stream(smpc_robot_sim * sim, smpc_handle * mpc)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!mpc)
+      return guarded([&] { sim->e->adopt_stream(sim->e->stream, true); });
+    if (mpc->e->device_id != sim->e->device_id)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_share_stream: the simulator and the MPC handle live on different devices");
+    return guarded([&] { sim->e->adopt_stream(mpc->e->stream, false); });
+  }
+  int smpc_robot_sim_forward_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, const unsigned * contact_mask, const double * Kp,
+                                      const double * Kd, double prox_accuracy, double prox_mu, int prox_max_iter, double * a_out, double * lambda_out,
+                                      int * iters_out)
+  {
+    if (!sim || !X || !tau || !contact_mask || !a_out || !lambda_out)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (n < 1)
+      return fail(SMPC_ERR_INVALID, "n must be positive");
+    return guarded([&] { sim->e->forward_dynamics(n, X, tau, contact_mask, Kp, Kd, prox_accuracy, prox_mu, prox_max_iter, a_out, lambda_out, iters_out); });
+  }
+  int smpc_robot_sim_step_device(smpc_robot_sim * sim, double * X_device, const double * tau_device, const uint8_t * contact, const uint32_t * mask_device,
+                                 const double * Kp, const double * Kd, double dt)
+  {
+    if (!sim || !X_device || !tau_device || (!contact && !mask_device))
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!(dt > 0.0))
+      return fail(SMPC_ERR_INVALID, "dt must be positive");
+    const unsigned mask_all = contact ? contact_bits(contact, sim->e->sz.nfeet) : 0u;
+    return guarded([&] { sim->e->step_device(X_device, tau_device, mask_all, mask_device, Kp, Kd, dt); });
+  }
+  int smpc_robot_sim_get_last(smpc_robot_sim * sim, double ** a_device, double ** lambda_device)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (a_device)
+      *a_device = sim->e->a;
+    if (lambda_device)
+      *lambda_device = sim->e->lam;
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_read_last(smpc_robot_sim * sim, double * a_out, double * lambda_out)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { sim->e->read_last(a_out, lambda_out); });
   }
 }

@@ -60,20 +60,20 @@ namespace smpc
 
   SMPC_HD double id_rt_dot6(const double * s, const double * f) { return s[0] * f[0] + s[1] * f[1] + s[2] * f[2] + s[3] * f[3] + s[4] * f[4] + s[5] * f[5]; }
 
-  // ---- kernel 1: rigid-body quantities on the run-time tree ----   grid = B, 64 lanes
-  SMPC_DEV void id_quant_rt_body(const IdRtBuffers & b, int block)
+  // ---- the tree walk both kernels on a run-time tree share (id_quant_rt_body here, sim_rt_body of smpc_sim_rt.h) ----
+  // From one state `x` ([2 nj + 11], device) into `sc`: placements, motion-subspace columns, spatial velocities and bias accelerations of every
+  // joint (one step per tree level), body inertias and forces f = I (a - g) + v x* (I v) under the gravity field g, foot positions, the
+  // sums over the subtree of every joint through the ancestor bit sets, F_d = Ic S_d and h_d = S_d . f (the bias forces).  Its first phase
+  // issues every global load it makes; it stores nothing outside `sc`.
+  SMPC_DEV void rt_tree_phases(IdQuantRtScratch & sc, const IdRtDevModel & mi, const double * x, const V3 g)
   {
     typedef IdQuantRtScratch SC;
     constexpr int NT = 64, MAXJ = SC::MAXJ, MAXV = SC::MAXV, NF = SC::NF;
     static_assert(MAXJ <= 32 && MAXV <= NT, "lane = joint below 32, lane - 32 = foot, lane = degree of freedom");
-    const int inst = block;
-    const IdRtDevModel & mi = *b.model;
     const RtDevModel & mg = mi.t;
     const int nj = mg.njoints < MAXJ ? (mg.njoints > 1 ? mg.njoints : 1) : MAXJ;
     const int nlev = mg.nlevels < MAXJ ? mg.nlevels : MAXJ;
     const int nv = nj + 5, nq = nj + 6, nx = 2 * nj + 11;
-    SMPC_LDS(SC, scs, 1);
-    SC & sc = scs[0];
     SMPC_PLA(double, jg, NT, 22); // jpR 0..8 | jpp 9..11 | mass 12 | com 13..15 | inertia 16..21 of this lane's joint
     SMPC_PLA(double, fp, NT, 3);
     SMPC_PL(int, par, NT);
@@ -107,7 +107,7 @@ namespace smpc
       for (int i = 0; i < 3; i++)
         SMPC_PLV(fp)[i] = mg.foot_p[f][i];
       for (int i = lane; i < nx; i += NT)
-        sc.x[i] = b.X[(size_t)inst * nx + i];
+        sc.x[i] = x[i];
       if (lane < MAXJ)
         sc.anc[lane] = lane < nj ? an : 0u;
       if (lane >= 32 && lane < 32 + NF)
@@ -195,7 +195,7 @@ namespace smpc
       I.jzz = Iw.a22 + m * (cc - c.z * c.z);
       stsi(&sc.body[j * 10], I);
       SV a = ldsv(&sc.acc[j * 6]);
-      a.l.z += 9.81; // gravity -9.81 along z as an acceleration of the world
+      a.l = a.l - g; // the gravity field as an acceleration of the world
       stsv(&sc.fb[j * 6], I * a + crf(v, I * v));
     }
     else if (lane >= 32 && lane < 32 + NF)
@@ -230,6 +230,21 @@ namespace smpc
       sc.h[d] = id_rt_dot6(&sc.S[d * 6], &sc.fs[jd * 6]);
     }
     SMPC_LANES_END_WAVE
+  }
+
+  // ---- kernel 1: rigid-body quantities on the run-time tree ----   grid = B, 64 lanes
+  SMPC_DEV void id_quant_rt_body(const IdRtBuffers & b, int block)
+  {
+    typedef IdQuantRtScratch SC;
+    constexpr int NT = 64, MAXJ = SC::MAXJ, NF = SC::NF;
+    const int inst = block;
+    const IdRtDevModel & mi = *b.model;
+    const int nj = mi.t.njoints < MAXJ ? (mi.t.njoints > 1 ? mi.t.njoints : 1) : MAXJ;
+    const int nv = nj + 5, nx = 2 * nj + 11;
+    SMPC_LDS(SC, scs, 1);
+    SC & sc = scs[0];
+    // ---- phases 0 .. 4 ----
+    rt_tree_phases(sc, mi, b.X + (size_t)inst * nx, mk3(0.0, 0.0, -9.81));
     // ---- phase 5: every global store ----
     SMPC_LANES(NT)
     {

@@ -158,6 +158,7 @@ SYMBOLS = [
     "smpc_debug_get_steps", "smpc_debug_get_terminal", "smpc_debug_get_phase_cycles", "smpc_set_profiling", "smpc_get_kernel_times", "smpc_get_kernel_times_n", "smpc_kernel_time_slots", "smpc_reset_kernel_times",
     "smpc_interpolate", "smpc_interpolate_knots", "smpc_friction_compensation", "smpc_update_internal_data", "smpc_debug_frontend_rt", "smpc_full_forward_dynamics", "smpc_centroidal_dynamics", "smpc_riccati_feedback",
     "smpc_id_create", "smpc_id_destroy", "smpc_id_set_target", "smpc_id_set_targets", "smpc_id_set_target_centroidal", "smpc_id_set_targets_centroidal", "smpc_id_solve", "smpc_id_solve_device", "smpc_id_wait", "smpc_id_get_resid", "smpc_id_reset", "smpc_id_get_tau_device", "smpc_id_get_x_device", "smpc_id_set_targets_from_mpc", "smpc_id_share_stream", "smpc_sim_step_device", "smpc_id_debug_get", "smpc_id_get_dims", "smpc_debug_id_force_rt",
+    "smpc_robot_sim_create", "smpc_robot_sim_destroy", "smpc_robot_sim_get_dims", "smpc_robot_sim_wait", "smpc_robot_sim_get_stream", "smpc_robot_sim_share_stream", "smpc_robot_sim_forward_dynamics", "smpc_robot_sim_step_device", "smpc_robot_sim_get_last", "smpc_robot_sim_read_last",
 ]
 
 
@@ -281,6 +282,18 @@ class SmpcLib:
         L.smpc_debug_frontend_rt.argtypes = [vp, _dp, vp, vp, vp, vp]
         L.smpc_full_forward_dynamics.argtypes = [vp, C.c_int, _dp, _dp, vp, vp, vp, C.c_double, C.c_double, C.c_int, _dp, _dp, vp, vp]
         L.smpc_interpolate_knots.argtypes = [C.c_int, C.c_double, C.c_double, _dp, C.c_int, C.c_int, _dp, C.c_int]
+        L.smpc_robot_sim_create.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(vp)]
+        L.smpc_robot_sim_destroy.argtypes = [vp]
+        L.smpc_robot_sim_destroy.restype = None
+        L.smpc_robot_sim_get_dims.argtypes = [vp, C.POINTER(C.c_int)]
+        L.smpc_robot_sim_wait.argtypes = [vp]
+        L.smpc_robot_sim_get_stream.argtypes = [vp]
+        L.smpc_robot_sim_get_stream.restype = C.c_void_p
+        L.smpc_robot_sim_share_stream.argtypes = [vp, vp]
+        L.smpc_robot_sim_forward_dynamics.argtypes = [vp, C.c_int, _dp, _dp, vp, vp, vp, C.c_double, C.c_double, C.c_int, _dp, _dp, vp]
+        L.smpc_robot_sim_step_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_double]
+        L.smpc_robot_sim_get_last.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.smpc_robot_sim_read_last.argtypes = [vp, vp, vp]
 
     def check(self, code):
         if code < 0:

@@ -1,0 +1,89 @@
+"""Launch times of the simulator step: the templated pair of a kinodynamics handle (full_fd_body + sim_integrate_body) and the one-launch
+kernel on a run-time joint tree (sim_rt_body) side by side.
+
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -o sim -- python3 tools/sim_rt_profile.py run [batch]
+    python3 tools/sim_rt_profile.py summary <kernel_trace.csv> [batch]
+
+`run`: go2_like through BatchedMPC.simStepDevice of a kinodynamics handle (the yardstick), then BatchedRobotSim.stepDevice on go2_like,
+quad_arm, the 32-joint point-foot table of tests/test_id_any_robot.py and tree32 with two 6-D contacts, one after the other; every foot in
+contact, Baumgarte gains (0, 50), small random torques; per robot WARM steps, then READINGS x LAUNCHES steps -- the states move between
+launches because every step integrates them.  `summary`: the dispatches of the trace whose grid is the full batch, per kernel in launch
+order, cut into the robots' runs; per reading the mean of its LAUNCHES dispatches, then the minimum of the readings and their spread."""
+import collections
+import csv
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WARM, READINGS, LAUNCHES = 5, 3, 20
+RUNS = [("go2_like", 3, False), ("go2_like", 3, True), ("quad_arm", 3, True), ("tree32p", 3, True), ("tree32", 6, True)]  # (robot, contact size, run-time kernel)
+
+
+def run(B):
+    sys.path[:0] = [os.path.join(ROOT, "simple-mpc_amd", "python"), os.path.join(ROOT, "tests")]
+    import numpy as np
+    import torch
+    import mpc_setup as S
+    import robot_tables as RT
+    import simple_mpc
+    import test_id_any_robot as T
+
+    for name, fs, rt in RUNS:
+        tab = T.table(name)
+        rb = RT.oracle_robot(tab)
+        if rt:
+            sim = simple_mpc.BatchedRobotSim(RT.model_handler(tab), force_size=fs, batch=B)
+            step = lambda x, t: sim.stepDevice(x, t, [True] * tab.nfeet, 1e-3, Kp=[0.0] * fs, Kd=[50.0] * fs)
+        else:
+            sim = S.make_product(B)[0]
+            step = lambda x, t: sim.simStepDevice(x, t, [True] * 4, 1e-3, Kp=[0.0] * 3, Kd=[50.0] * 3)
+        X = RT.near_reference_states(rb, min(B, 64), seed=5, scale=0.3)
+        X = np.tile(X, (-(-B // X.shape[0]), 1))[:B]
+        Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
+        td = torch.from_numpy(np.random.default_rng(6).normal(0.0, 1.0, (B, rb.nv - 6))).cuda()
+        torch.cuda.synchronize()
+        for _ in range(WARM + READINGS * LAUNCHES):
+            step(Xd.data_ptr(), td.data_ptr())
+        sim.wait()
+        Xh = Xd.cpu().numpy()
+        print(name, "fs", fs, "run-time" if rt else "templated", "finite:", bool(np.isfinite(Xh).all()), "largest state change %.3f" % np.abs(Xh - X).max(), flush=True)
+
+
+def summary(trace, B):
+    fam = collections.defaultdict(list)  # kernel -> durations in launch order
+    for r in sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"])):
+        grid = int(r["Grid_Size"]) if "Grid_Size" in r else int(r["Grid_Size_X"])
+        m = re.search(r"(sim_rt_body|full_fd_body|sim_integrate_body)", r["Kernel_Name"])
+        if m and grid == B * 64:
+            fam[m.group(1)].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3)
+    per = WARM + READINGS * LAUNCHES
+
+    def reading(d):
+        means = [sum(d[i * LAUNCHES: (i + 1) * LAUNCHES]) / LAUNCHES for i in range(READINGS)]
+        return min(means), max(means) / min(means) - 1.0
+
+    print("| robot | contacts | kernels | step µs | spread of the readings |")
+    print("|---|---|---|---|---|")
+    k, yard = 0, None
+    for name, fs, rt in RUNS:
+        if rt:
+            d = fam["sim_rt_body"]
+            assert len(d) == per * sum(r for _, _, r in RUNS), len(d)
+            t, sp = reading(d[k * per + WARM: (k + 1) * per])
+            ratio = "" if yard is None or name != "go2_like" else " (%.2fx the yardstick)" % (t / yard)
+            print("| %s | %d-D | `sim_rt_body` | %.1f%s | %.1f %% |" % (name, fs, t, ratio, 100 * sp))
+            k += 1
+        else:
+            a, b = fam["full_fd_body"], fam["sim_integrate_body"]
+            assert len(a) >= per and len(b) >= per, (len(a), len(b))
+            (ta, sa), (tb, sb) = reading(a[-per:][WARM:]), reading(b[-per:][WARM:])
+            yard = ta + tb
+            print("| %s (yardstick) | %d-D | `full_fd_body` %.1f + `sim_integrate_body` %.1f | %.1f | %.1f %% |" % (name, fs, ta, tb, yard, 100 * max(sa, sb)))
+
+
+if __name__ == "__main__":
+    if sys.argv[1] == "run":
+        run(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+    else:
+        summary(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 4096)
