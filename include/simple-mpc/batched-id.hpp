@@ -112,7 +112,7 @@ namespace simple_mpc
         throw std::runtime_error("flat feet: quad_contact_points must hold the four corners of every sole ([nfeet][4][3])");
       c.force_size = fs_;
       c.quad_contact_points = fs_ == 6 ? s.quad_contact_points.data() : nullptr;
-      check(smpc_id_create(robot, &c, batch, device_id, &h_));
+      check(smpc_id_create_any(robot, &c, batch, device_id, &h_)); // (every robot smpc_id_create serves + flat feet on any validated table)
     }
     static void check(int rc)
     {

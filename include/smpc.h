@@ -522,7 +522,7 @@ int smpc_id_debug_get(smpc_id_handle * h, int what, double * out);
  * any pinocchio::Model in KinodynamicsID / CentroidalID (src/inverse-dynamics/kinodynamics-id.cpp:7-237, centroidal-id.cpp:6-147).
  * smpc_id_create keeps its two built shapes (13 joints / 4 point feet, 23 joints / 2 flat feet) on their templated kernels; every other
  * point-foot table is validated like the centroidal MPC's (SMPC_ERR_INVALID naming the field, nothing allocated) and served by kernels
- * that read the joint tree at run time.  Flat feet on any other tree are refused.
+ * that read the joint tree at run time.  Flat feet on any other tree are refused by smpc_id_create and served by smpc_id_create_any (below).
  *   smpc_id_get_dims        dims[10] = B, nq, nv, nfeet, force size of a target, n (variables), m (rows), n and m padded to 16, contact-
  *                           motion rows per foot: what the buffers of this section are sized by (kinodynamics-id.cpp:24-38 reads them
  *                           from the model)
@@ -530,9 +530,16 @@ int smpc_id_debug_get(smpc_id_handle * h, int what, double * out);
  *                           returns the previous setting.  One process-wide atomic flag: a handle created by another thread while it is
  *                           set takes the run-time kernels as well.
  * The limit vectors of smpc_id_settings are raw pointers: the C ABI reads nv - 6 entries of each and cannot check their lengths; the
- * Python and C++ mirrors, which hold the containers, refuse a vector of another length before they call smpc_id_create. */
+ * Python and C++ mirrors, which hold the containers, refuse a vector of another length before they call smpc_id_create_any. */
 int smpc_id_get_dims(smpc_id_handle * h, int * dims);
 int smpc_debug_id_force_rt(int on);
+/* everything smpc_id_create accepts, served by the same engines and kernel symbols, plus: flat feet (force_size 6, 2 feet) on any validated
+ * table with 2 .. SMPC_MAX_JOINTS joints, served by the run-time flat-foot engine (n = nv + 24 variables, m = n + 52 + nv - 6 rows; wrench
+ * targets [2][6]).  A table it refuses: SMPC_ERR_INVALID naming the field (parent[5], njoints, "nfeet = 4 ... built for 2 flat feet"), nothing
+ * allocated.  There are two entries because smpc_id_create's answer to flat feet on any other tree than the built one -- the refusal above -- is
+ * pinned by existing callers and tests; the mirrors call this one.  Under smpc_debug_id_force_rt(1) this entry also sends the built flat-foot shape
+ * (23 joints / 2 flat feet) through the run-time engine.  smpc_id_debug_get, what = 13: foot rotations [B][nfeet][9] (run-time flat-foot engine). */
+int smpc_id_create_any(const smpc_robot_model * robot, const smpc_id_settings * settings, int batch, int device_id, smpc_id_handle ** out);
 
 /* ---- batched rigid-body simulator for any robot table (simple-mpc_amd/csrc/smpc_sim_rt.h) ----
  * A stand-alone handle that carries a robot table and nothing else (no OCP, no MPC settings): the constrained forward dynamics of

@@ -964,7 +964,8 @@ extern "C"
 
   // ---- whole-body inverse-dynamics QP (smpc_id.h, smpc_id_rt.h) ----
   static std::atomic<int> g_id_force_rt{0}; // (process-wide; read once per smpc_id_create)
-  int smpc_id_create(const smpc_robot_model * robot, const smpc_id_settings * c, int batch, int device_id, smpc_id_handle ** out)
+  // the one body of smpc_id_create and smpc_id_create_any: only the routing call differs
+  static int id_create_routed(const smpc_robot_model * robot, const smpc_id_settings * c, int batch, int device_id, smpc_id_handle ** out, bool any)
   {
     if (!robot || !c || !out)
       return fail(SMPC_ERR_INVALID, "null argument");
@@ -1008,7 +1009,9 @@ extern "C"
     // the two built shapes keep their templated engines and kernel symbols; every other table with 4 point feet: the engine on the run-time
     // joint tree (smpc_id_rt.h), on a table that is checked before anything is allocated for it
     std::string why;
-    const IdRoute route = id_route(robot, quad, FullGo2::NJ, FullGo2::NF, FullTalos::NJ, FullTalos::NF, g_id_force_rt.load() != 0, why);
+    const bool force_rt = g_id_force_rt.load() != 0;
+    const IdRoute route = any ? id_route_any(robot, quad, FullGo2::NJ, FullGo2::NF, FullTalos::NJ, FullTalos::NF, force_rt, why)
+                              : id_route(robot, quad, FullGo2::NJ, FullGo2::NF, FullTalos::NJ, FullTalos::NF, force_rt, why);
     if (route == ID_ROUTE_REFUSED)
       return fail(SMPC_ERR_INVALID, why);
     const int na = robot->nv - 6;
@@ -1031,10 +1034,19 @@ extern "C"
       else if (route == ID_ROUTE_TALOS)
         *out = reinterpret_cast<smpc_id_handle *>(static_cast<IdEngineBase *>(new IdEngine<FullTalos>(robot, hs, batch, device_id)));
       else
-        *out = reinterpret_cast<smpc_id_handle *>(static_cast<IdEngineBase *>(new IdEngineRt(robot, hs, batch, device_id)));
+        *out = reinterpret_cast<smpc_id_handle *>(static_cast<IdEngineBase *>(new IdEngineRt(robot, hs, batch, device_id, route == ID_ROUTE_RT6)));
     });
   }
-  // debug: send the built point-foot shape (13 joints / 4 point feet) through the run-time engine too, so that the two can be compared
+  int smpc_id_create(const smpc_robot_model * robot, const smpc_id_settings * c, int batch, int device_id, smpc_id_handle ** out)
+  {
+    return id_create_routed(robot, c, batch, device_id, out, false);
+  }
+  int smpc_id_create_any(const smpc_robot_model * robot, const smpc_id_settings * c, int batch, int device_id, smpc_id_handle ** out)
+  {
+    return id_create_routed(robot, c, batch, device_id, out, true);
+  }
+  // debug: send the built point-foot shape (13 joints / 4 point feet) through the run-time engine too, so that the two can be compared; under
+  // smpc_id_create_any also the built flat-foot shape (23 joints / 2 flat feet)
   int smpc_debug_id_force_rt(int on)
   {
     return g_id_force_rt.exchange(on != 0 ? 1 : 0);
@@ -1090,7 +1102,7 @@ extern "C"
       if (!a)
         ta.resize((size_t)e->B * e->nv);
       if (!f)
-        tf.resize((size_t)e->B * 3 * e->nf);
+        tf.resize((size_t)e->B * e->nfw * e->nf);
       e->solve(X, tau, a ? a : ta.data(), f ? f : tf.data(), resid);
     });
   }

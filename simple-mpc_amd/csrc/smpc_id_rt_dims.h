@@ -1,6 +1,6 @@
 // smpc_id_rt_dims.h -- host-side sizes and admission of the inverse-dynamics QP on a RUN-TIME joint tree (smpc_id_rt.h): which engine a
-// robot table goes to, the problem sizes of a point-foot robot, the ancestor sets of its joints.  Plain C++ with no backend behind it, so
-// that a stand-alone host program can exercise it (tests/cpp/id_rt_dims_check.cpp).
+// robot table goes to, the problem sizes of a point-foot and of a flat-foot robot, the ancestor sets of its joints.  Plain C++ with no backend
+// behind it, so that stand-alone host programs can exercise it (tests/cpp/id_rt_dims_check.cpp, tests/cpp/id_rt6_dims_check.cpp).
 #pragma once
 #include "smpc_robot_check.h"
 #include <vector>
@@ -36,7 +36,8 @@ namespace smpc
     ID_ROUTE_GO2 = 0,   // 13 joints / 4 point feet: IdEngine<FullGo2>
     ID_ROUTE_TALOS = 1, // 23 joints / 2 flat feet: IdEngine<FullTalos>
     ID_ROUTE_RT = 2,    // any other validated table with 4 point feet: IdEngineRt
-    ID_ROUTE_REFUSED = 3
+    ID_ROUTE_REFUSED = 3,
+    ID_ROUTE_RT6 = 4    // id_route_any only: any other validated table with 2 flat feet: IdEngineRt on its flat-foot kernels
   };
   // which engine smpc_id_create builds for a table; `why` receives the refusal.  force_rt: the debug switch that sends the built point-foot
   // shape through the run-time engine.  Nothing is allocated before this has answered.
@@ -64,6 +65,56 @@ namespace smpc
       return ID_ROUTE_REFUSED;
     }
     return ID_ROUTE_RT;
+  }
+
+  // ---- flat feet (tsid Contact6d) on a run-time joint tree: 2 feet, 12 corner-force variables, 6 LOCAL motion rows, 17 friction / bound rows each ----
+  constexpr int ID_RT6_NFEET = 2;
+  constexpr int ID_RT6_NFV = 12, ID_RT6_NM = 6, ID_RT6_NFR = 17;
+  constexpr int ID_RT6_MAX_N = ID_RT_MAX_NV + ID_RT6_NFV * ID_RT6_NFEET;            // 61 variables [a ; corner forces]
+  constexpr int ID_RT6_FR = ID_RT6_NFR * ID_RT6_NFEET;                              // 34 friction rows (closed form in the solver)
+  constexpr int ID_RT6_MAX_DR = 6 + ID_RT6_NM * ID_RT6_NFEET + ID_RT_MAX_NV - 6;    // 49 dense general rows: dynamics | contact motion | actuation
+
+  struct IdRt6Sizes
+  {
+    int nq, nv, na, nf, n, m, np, mp, gr, dr, fr; // n = nv + 24 ; m = n + 6 + 12 + 34 + na ; padded to multiples of 16 ; gr = m - n = dr + fr
+  };
+  inline IdRt6Sizes id_rt6_sizes(int njoints)
+  {
+    IdRt6Sizes s;
+    s.nq = njoints + 6;
+    s.nv = njoints + 5;
+    s.na = s.nv - 6;
+    s.nf = ID_RT6_NFEET;
+    s.n = s.nv + ID_RT6_NFV * s.nf;
+    s.dr = 6 + ID_RT6_NM * s.nf + s.na;
+    s.fr = ID_RT6_FR;
+    s.m = s.n + s.dr + s.fr;
+    s.np = ((s.n + 15) / 16) * 16;
+    s.mp = ((s.m + 15) / 16) * 16;
+    s.gr = s.m - s.n;
+    return s;
+  }
+
+  // which engine smpc_id_create_any builds: id_route for every input but one -- flat feet on a shape that is not the built one (or on the
+  // built one under force_rt) go to the run-time flat-foot engine, once robot_table_error has accepted the table and it has 2 feet.
+  // Nothing is allocated before this has answered.
+  inline IdRoute id_route_any(const smpc_robot_model * rm, bool flat_feet, int go2_nj, int go2_nf, int talos_nj, int talos_nf, bool force_rt, std::string & why)
+  {
+    const bool built = rm->njoints == talos_nj && rm->nfeet == talos_nf;
+    if (!flat_feet || (built && !force_rt))
+      return id_route(rm, flat_feet, go2_nj, go2_nf, talos_nj, talos_nf, force_rt, why);
+    why = robot_table_error(rm);
+    if (!why.empty())
+      return ID_ROUTE_REFUSED;
+    if (rm->nfeet != ID_RT6_NFEET)
+    {
+      char b[200];
+      std::snprintf(b, sizeof(b), "robot table: nfeet = %d, the inverse-dynamics engine for flat feet (force size 6) on a run-time joint tree is built for %d flat feet",
+                    rm->nfeet, ID_RT6_NFEET);
+      why = b;
+      return ID_ROUTE_REFUSED;
+    }
+    return ID_ROUTE_RT6;
   }
 
   // limit vectors of the actuated joints: nv - 6 entries each

@@ -1260,7 +1260,7 @@ class KinodynamicsID:
             self._quad = np.ascontiguousarray(np.stack([quads[n] for n in names]), float)
             c.force_size, c.quad_contact_points, self._fs = 6, self._quad.ctypes.data, 6
         h = C.c_void_p()
-        self._lib.check(self._lib.L.smpc_id_create(model_handler._ptr, C.byref(c), self.B, device_id, C.byref(h)))
+        self._lib.check(self._lib.L.smpc_id_create_any(model_handler._ptr, C.byref(c), self.B, device_id, C.byref(h)))
         self._h = h
         self._nq, self._nv, self._nf = model_handler.nq, model_handler.nv, model_handler.getFeetNb()
         self._a = np.zeros((self.B, self._nv))
@@ -1353,7 +1353,7 @@ class KinodynamicsID:
         m = n + 6 + nm + (17 if self._fs == 6 else 4) * self._nf + self._nv - 6
         npad, mpad = (n + 15) // 16 * 16, (m + 15) // 16 * 16
         per = {0: (self._nv, self._nv), 1: (self._nv,), 2: (nm, self._nv), 3: (nm,), 4: (nm,), 5: (npad, npad), 6: (npad,),
-               7: (mpad, npad), 8: (mpad,), 9: (mpad,), 10: (3,), 11: (3 * self._nf,), 12: (self._nv - 6,)}[what]
+               7: (mpad, npad), 8: (mpad,), 9: (mpad,), 10: (3,), 11: (3 * self._nf,), 12: (self._nv - 6,), 13: (self._nf, 9)}[what]
         out = np.zeros((self.B,) + per)
         self._lib.check(self._lib.L.smpc_id_debug_get(self._h, what, out))
         return out

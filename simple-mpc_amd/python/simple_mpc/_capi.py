@@ -157,7 +157,7 @@ SYMBOLS = [
     "smpc_set_early_exit_on_tol", "smpc_iterate_async", "smpc_gather_outputs", "smpc_gather_outputs_device", "smpc_gather_outputs_peer", "smpc_get_foot_timing", "smpc_get_info", "smpc_get_status", "smpc_get_cold_trace", "smpc_lq_size", "smpc_debug_get_lq",
     "smpc_debug_get_steps", "smpc_debug_get_terminal", "smpc_debug_get_phase_cycles", "smpc_set_profiling", "smpc_get_kernel_times", "smpc_get_kernel_times_n", "smpc_kernel_time_slots", "smpc_reset_kernel_times",
     "smpc_interpolate", "smpc_interpolate_knots", "smpc_friction_compensation", "smpc_update_internal_data", "smpc_debug_frontend_rt", "smpc_full_forward_dynamics", "smpc_centroidal_dynamics", "smpc_riccati_feedback",
-    "smpc_id_create", "smpc_id_destroy", "smpc_id_set_target", "smpc_id_set_targets", "smpc_id_set_target_centroidal", "smpc_id_set_targets_centroidal", "smpc_id_solve", "smpc_id_solve_device", "smpc_id_wait", "smpc_id_get_resid", "smpc_id_reset", "smpc_id_get_tau_device", "smpc_id_get_x_device", "smpc_id_set_targets_from_mpc", "smpc_id_share_stream", "smpc_sim_step_device", "smpc_id_debug_get", "smpc_id_get_dims", "smpc_debug_id_force_rt",
+    "smpc_id_create", "smpc_id_create_any", "smpc_id_destroy", "smpc_id_set_target", "smpc_id_set_targets", "smpc_id_set_target_centroidal", "smpc_id_set_targets_centroidal", "smpc_id_solve", "smpc_id_solve_device", "smpc_id_wait", "smpc_id_get_resid", "smpc_id_reset", "smpc_id_get_tau_device", "smpc_id_get_x_device", "smpc_id_set_targets_from_mpc", "smpc_id_share_stream", "smpc_sim_step_device", "smpc_id_debug_get", "smpc_id_get_dims", "smpc_debug_id_force_rt",
     "smpc_robot_sim_create", "smpc_robot_sim_destroy", "smpc_robot_sim_get_dims", "smpc_robot_sim_wait", "smpc_robot_sim_get_stream", "smpc_robot_sim_share_stream", "smpc_robot_sim_forward_dynamics", "smpc_robot_sim_step_device", "smpc_robot_sim_get_last", "smpc_robot_sim_read_last",
 ]
 
@@ -221,6 +221,7 @@ class SmpcLib:
         L.smpc_get_contact_state.argtypes = [vp, C.c_int, _bp]
         L.smpc_get_cycling_contact_state.argtypes = [vp, C.c_int, C.c_void_p]
         L.smpc_id_create.argtypes = [vp, C.POINTER(IdSettingsC), C.c_int, C.c_int, C.POINTER(vp)]
+        L.smpc_id_create_any.argtypes = [vp, C.POINTER(IdSettingsC), C.c_int, C.c_int, C.POINTER(vp)]
         L.smpc_id_destroy.argtypes = [vp]
         L.smpc_id_destroy.restype = None
         L.smpc_id_set_target.argtypes = [vp, C.c_int, _dp, _dp, _dp, _bp, _dp]

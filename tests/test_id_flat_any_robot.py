@@ -1,0 +1,402 @@
+"""Inverse-dynamics QP controllers (KinodynamicsID, CentroidalID) for any robot table with 2 flat feet (tsid Contact6d): the flat-foot kernels
+on a run-time joint tree (simple-mpc_amd/csrc/smpc_id_rt.h: id6_quant_rt_body, id6_assemble_rt_body, qp6_admm_rt_body) against the oracle
+(oracle/orc_id.hpp with force_size = 6, run-time sized on the same struct), on biped_legs (13 joints: Go2's joint count with another foot type,
+n = 42, m = 106), tree32 (32 joints, feet on joints 30 / 31: the bound of every array, n = 61, m = 144) and talos_like through the debug switch
+(the built shape otherwise keeps its templated kernels).  The engine is reached through smpc_id_create_any, which the public classes call;
+smpc_id_create keeps its refusal of flat feet on a run-time tree.
+
+CPU tier: the kernel bodies compiled with the sequential-lane test backend (tests/emu); tests/test_id_flat_any_robot_gpu.py runs the same
+helpers on the HIP library.  Bars: quantities 1e-11 relative (tests/test_id_any_robot.py); H, g 1e-12, general rows of C 1e-11, finite l, u
+1e-9 (tests/test_inverse_dynamics_quad.py::_device); solution after 100 cold iterations 1e-8; warm-started ticks 1e-6 emulated / 1e-5 on the
+GPU; default stopping rule 1e-4."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import mpc_setup as S
+import oracle_lib as O
+import robot_tables as RT
+import simple_mpc
+from simple_mpc import RobotModelC
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "golden"))
+import make_golden_id_quad as M  # noqa: E402  (settings and integration step of the flat-foot fixture)
+
+DT = M.DT
+ROBOTS = ["biped_legs", "tree32"]
+KEYS, CKEYS = simple_mpc.KinodynamicsID._KEYS, simple_mpc.CentroidalID._KEYS
+KINO = dict(M.KINO, w_contact_force=1e-3)
+CENT = dict(M.CENT, w_contact_force=1e-3)
+_INVALID = -1  # SMPC_ERR_INVALID (include/smpc.h)
+
+
+def limits(name):
+    """Effort / velocity limits in the table's joint order (O.TALOS_EFFORT / O.TALOS_VMAX are indexed by talos_like joint - 1)."""
+    if name == "talos_like":
+        return O.TALOS_EFFORT.copy(), O.TALOS_VMAX.copy()
+    if name == "biped_legs":
+        return O.TALOS_EFFORT[:12].copy(), O.TALOS_VMAX[:12].copy()
+    assert name == "tree32"
+    src = {1: 13, 2: 14}
+    src.update({3 + i: 15 + i for i in range(4)})
+    src.update({10 + i: 19 + i for i in range(4)})
+    for k in range(6):  # the legs are interleaved on joints 20 .. 31
+        src[20 + 2 * k], src[21 + 2 * k] = 1 + k, 7 + k
+    tau, vmax = np.full(31, 30.0), np.full(31, 20.0)  # (joints 7 - 9, 14 - 19: the table's own)
+    for j, k in src.items():
+        tau[j - 1], vmax[j - 1] = O.TALOS_EFFORT[k - 1], O.TALOS_VMAX[k - 1]
+    return tau, vmax
+
+
+def wrenches(rb, contact=(True, True)):
+    """Static wrench targets: the weight shared by the feet in contact, [2][6]."""
+    w = np.zeros((2, 6))
+    for k, on in enumerate(contact):
+        if on:
+            w[k, 2] = rb.mass * 9.81 / sum(contact)
+    return w
+
+
+def make(name, lib, B, admm_iters=100, admm_tol=-1.0, oracle=True, **kw):
+    """(robot, oracle, product) on one table; talos_like goes through the run-time engine (smpc_debug_id_force_rt)."""
+    tab = RT.table(name)
+    rb = RT.oracle_robot(tab)
+    tau_max, v_max = limits(name)
+    flags = {k: kw.pop(k) for k in ("base_reference_as_coded", "tsid_joint_bounds") if k in kw}
+    s = O.id_settings(rb, DT, tau_max=tau_max, v_max=v_max, admm_iters=admm_iters, admm_tol=admm_tol, force_size=6,
+                      quad_points=np.tile(RT.QUAD, (2, 1, 1)), **kw, **flags)
+    ok = O.OracleKinoID(rb, s, B) if oracle else None
+    mh = RT.model_handler(tab, lib)
+    L = (lib or simple_mpc.default_lib()).L
+    was = L.smpc_debug_id_force_rt(1)
+    try:
+        cls, keys = (simple_mpc.CentroidalID, CKEYS) if s["centroidal"] else (simple_mpc.KinodynamicsID, KEYS)
+        gk = cls(mh, DT, {k: s[k] for k in keys}, tau_max, v_max, batch=B, lib=lib, admm_iters=admm_iters, admm_tol=admm_tol, **flags)
+    finally:
+        L.smpc_debug_id_force_rt(was)
+    return rb, ok, gk
+
+
+def dims(gk):
+    d = (C.c_int * 10)()
+    gk._lib.check(gk._lib.L.smpc_id_get_dims(gk._h, d))
+    return dict(zip(("B", "nq", "nv", "nf", "nfw", "n", "m", "np", "mp", "nmot"), d))
+
+
+def _rot(qxyzw):
+    x, y, z, w = qxyzw
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def compare_qp(rb, ok, gk, X, worst):
+    n, m = ok.n, ok.m
+    dbg = {w: gk.debug(w) for w in range(14)}
+    for b in range(X.shape[0]):
+        Q = O.id_quantities6(rb, X[b])
+        c = rb.centroidal(X[b])
+        Q["com"], Q["footp"] = c["com"], c["feet"].reshape(-1)
+        # foot rotations from the oracle's LOCAL angular rows: their base-rotation columns are R_f^T R_b
+        Rb = _rot(X[b, 3:7])
+        Q["footR"] = np.stack([Rb @ Q["J"][6 * f + 3: 6 * f + 6, 3:6].T for f in range(2)]).reshape(2, 9)
+        for what, key in ((0, "M"), (1, "nle"), (2, "J"), (3, "Jdv"), (4, "vfoot"), (10, "com"), (11, "footp"), (13, "footR")):
+            worst[key] = max(worst.get(key, 0.0), S.rel_err(Q[key], dbg[what][b]))
+        H, g, Cm, l, u = ok.qp(b, X[b])
+        worst["H"] = max(worst.get("H", 0.0), S.rel_err(H, dbg[5][b][:n, :n]))
+        worst["g"] = max(worst.get("g", 0.0), S.rel_err(g, dbg[6][b][:n]))
+        worst["C"] = max(worst.get("C", 0.0), float(np.abs(Cm[n:] - dbg[7][b][n:m, :n]).max() / max(1.0, np.abs(Cm).max())))
+        lg, ug = dbg[8][b][:m], dbg[9][b][:m]
+        assert np.array_equal(np.abs(l) > 1e19, np.abs(lg) > 1e19) and np.array_equal(np.abs(u) > 1e19, np.abs(ug) > 1e19)
+        fl, fu = np.abs(l) < 1e19, np.abs(u) < 1e19
+        worst["l"] = max(worst.get("l", 0.0), S.rel_err(l[fl], lg[fl]))
+        worst["u"] = max(worst.get("u", 0.0), S.rel_err(u[fu], ug[fu]))
+        # the padding: unit diagonal of H, zero gradient, zero columns and rows of C; the box rows are the identity
+        npad = dbg[5].shape[1]
+        assert np.array_equal(dbg[5][b][n:, n:], np.eye(npad - n)) and not dbg[5][b][:n, n:].any() and not dbg[6][b][n:].any() and not dbg[7][b][:, n:].any()
+        assert np.array_equal(dbg[7][b][:n, :n], np.eye(n)) and not dbg[7][b][m:].any()
+
+
+BARS = dict(H=1e-12, g=1e-12, C=1e-11, l=1e-9, u=1e-9, tau=1e-8, a=1e-8, f=1e-8)  # every other key (quantities): 1e-11
+
+
+SOLUTION = ("tau", "a", "f")
+
+
+def pieces(name, lib, centroidal, B=3, solution=False, **variant):
+    """Quantities, QP data and the solution after 100 iterations from a cold start: random states with non-zero velocities, robot 1 with its
+    right foot in the air (CentroidalID: the 6-D tracking task on, towards a displaced target).  Every figure is printed; `solution` chooses
+    which are asserted: the quantities and QP data, or tau / a / wrenches after the fixed work."""
+    rb, ok, gk = make(name, lib, B, centroidal=centroidal, **(CENT if centroidal else KINO), **variant)
+    X = RT.random_states(RT.table(name), B, seed=21, tilt=0.3, spread=0.5)
+    assert np.abs(X[:, rb.nq:]).min(1).max() > 1e-3
+    contact = [True, False]
+    w = wrenches(rb, contact)
+    if centroidal:
+        c = rb.centroidal(rb.x_ref)
+        feet, fv = c["feet"].copy(), np.zeros((2, 3))
+        feet[1] += [0.05, -0.05, 0.05]
+        fv[1] = [0.2, 0.0, 0.1]
+        ok.setTargetCentroidal(c["com"] + [0.01, 0.0, 0.02], [0.1, 0.0, -0.05], feet, fv, contact, w, instance=1)
+        gk.setTarget(c["com"] + [0.01, 0.0, 0.02], [0.1, 0.0, -0.05], feet, fv, contact, w, instance=1)
+    else:
+        xt = RT.random_states(RT.table(name), 1, seed=22, tilt=0.2, spread=0.3, vel=0.3)[0]
+        at = np.random.default_rng(23).normal(0, 1.0, rb.nv)
+        for k in (ok, gk):
+            k.setTarget(xt[: rb.nq], xt[rb.nq:], at, contact, w, instance=1)
+    to, ao, fo = ok.solve(X)
+    tg = gk.solve(0.0, X[:, : rb.nq], X[:, rb.nq:])
+    assert np.isfinite(tg).all()
+    worst = {}
+    compare_qp(rb, ok, gk, X, worst)
+    worst.update(tau=S.rel_err(to, tg), a=S.rel_err(ao, gk.getAccelerations()), f=S.rel_err(fo, gk.getContactForces().reshape(B, -1)))
+    print(name, "centroidal" if centroidal else "kinodynamics", variant, {k: "%.1e" % v for k, v in worst.items()},
+          "residuals oracle", ok.resid, "product", gk.resid)
+    for k, v in worst.items():
+        if (k in SOLUTION) == solution:
+            assert v < BARS.get(k, 1e-11), (name, k, v)
+    return worst
+
+
+def standing_loop(name, lib, n_steps, tol, B=1, resid_bars=False, **solver):
+    """Warm-started standing loop from x_ref; the oracle's accelerations advance the state both sides see (M.step)."""
+    rb, ok, gk = make(name, lib, B, **solver)
+    X = np.tile(rb.x_ref, (B, 1))
+    tau_max = limits(name)[0]
+    worst, first = 0.0, None
+    for i in range(n_steps):
+        to, ao, fo = ok.solve(X)
+        tg = gk.solve(0.0, X[:, : rb.nq], X[:, rb.nq:])
+        e = max(S.rel_err(to, tg), S.rel_err(ao, gk.getAccelerations()), S.rel_err(fo, gk.getContactForces().reshape(B, -1)))
+        if e >= tol and first is None:
+            first = i
+            print(name, "first tick beyond the bar:", i, "%.2e" % e, "residuals oracle / product", ok.resid, gk.resid)
+        worst = max(worst, e)
+        if resid_bars:
+            r = gk.getResiduals().max()
+            print(name, "tick", i, "residual %.2e" % r, "error %.2e" % e)
+            assert r < (1e-3 if i < 3 else 1e-5), (i, r)
+        assert np.all(np.abs(tg) <= tau_max + 1e-6)
+        X = np.stack([M.step(rb, X[b], ao[b]) for b in range(B)])
+    print(name, "standing loop", n_steps, solver, "worst %.1e" % worst)
+    assert worst < tol, (name, worst, first)
+    return worst
+
+
+def rt_vs_templated(lib, centroidal, B=3):
+    """talos_like through the debug switch (run-time flat-foot engine) against IdEngine<FullTalos> on the same inputs: the random states of the
+    point-foot sibling (seed 24); CentroidalID with the targets of the golden fixture (right foot in the air, tracked)."""
+    tab = RT.table("talos_like")
+    sett = CENT if centroidal else KINO
+    X = RT.random_states(tab, B, seed=24, tilt=0.3, spread=0.5)
+    rb, _, grt = make("talos_like", lib, B, oracle=False, centroidal=centroidal, **sett)
+    cls = simple_mpc.CentroidalID if centroidal else simple_mpc.KinodynamicsID
+    gt = cls(RT.model_handler(tab, lib), DT, sett, O.TALOS_EFFORT, O.TALOS_VMAX, batch=B, lib=lib, admm_iters=100, admm_tol=-1.0)
+    assert dims(grt)["np"] == 64 and dims(gt)["n"] == dims(grt)["n"] == 52
+    with pytest.raises(RuntimeError):
+        gt.debug(13)  # (the templated engine has no foot-rotation read-back: the two handles are different engines)
+    assert grt.debug(13).shape == (B, 2, 9)
+    if centroidal:
+        contact, w, com, feet = M.cent_targets(rb)
+        for k in (gt, grt):
+            k.setTarget(com, np.zeros(3), feet, np.zeros((2, 3)), contact, w)
+    ta = gt.solve(0.0, X[:, : rb.nq], X[:, rb.nq:])
+    tb = grt.solve(0.0, X[:, : rb.nq], X[:, rb.nq:])
+    worst = {}
+    for w in range(12):
+        key = "quant" if w < 5 or w > 9 else "qp"
+        a, b = gt.debug(w), grt.debug(w)
+        fin = np.abs(a) < 1e19
+        assert np.array_equal(fin, np.abs(b) < 1e19)
+        worst[key] = max(worst.get(key, 0.0), S.rel_err(a[fin], b[fin]))
+    worst["tau"] = S.rel_err(ta, tb)
+    assert np.isfinite(tb).all() and np.abs(tb).max() > 1e-3
+    print("run-time flat-foot engine vs templated engine, talos_like,", "centroidal" if centroidal else "kinodynamics",
+          {k: "%.1e" % v for k, v in worst.items()}, "residuals", gt.resid, grt.resid)
+    return worst
+
+
+def resident_targets(lib, B=3, ticks=10, tol=1e-8):
+    """smpc_id_set_targets_from_mpc + smpc_id_share_stream from a run-time centroidal MPC handle with 6-D feet (biped_legs, H = 10) against the
+    host-buffer path (setTargets of the interpolated solution, foot references and contact flags of stage 0) over `ticks` controller ticks."""
+    tab = RT.table("biped_legs")
+    mpc, rb, _, _ = RT.make_product(tab, B, 1, lib=lib, horizon=10)
+    mpc.generateCycleHorizon(RT.cycle(2))
+    V = np.zeros((B, 6))
+    V[:, 0] = np.linspace(0.05, 0.15, B)
+    mpc.switchToWalk(V[0])
+    mpc.setVelocityBaseBatched(V)
+    X = RT.near_reference_states(rb, B, seed=71, scale=0.3)
+    for _ in range(16):  # (the gait enters the horizon at its far end)
+        mpc.iterate(X)
+        if not all(mpc.ocp_handler.getContactState(0)):
+            break
+    contact = mpc.ocp_handler.getContactState(0)
+    assert not all(contact)  # (single support at stage 0: the tracking rows are on)
+    tau_max, v_max = limits("biped_legs")
+    mh = mpc.ocp_handler.model_handler
+    mk = lambda: simple_mpc.CentroidalID(mh, DT, CENT, tau_max, v_max, batch=B, lib=lib, admm_iters=100, admm_tol=-1.0)
+    ka, kb = mk(), mk()
+    assert dims(kb)["n"] == 42 and dims(kb)["nfw"] == 6
+    kb.shareStream(mpc)
+    refs = mpc.getReferencePoses()
+    worst = 0.0
+    for sub in range(ticks):
+        d = sub / float(ticks)
+        x_i, _, f_i = mpc.interpolate(d * 0.01)
+        assert f_i.shape == (B, 2, 6)
+        ka.setTargets(x_i[:, :3], x_i[:, 3:6] / rb.mass, (1 - d) * refs[:, 0] + d * refs[:, 1], (refs[:, 1] - refs[:, 0]) / 0.01, contact, f_i)
+        kb.setTargetsFromMPC(mpc, d * 0.01)
+        ta = ka.solve(0.0, X[:, : rb.nq], X[:, rb.nq:])
+        tb = kb.solve(0.0, X[:, : rb.nq], X[:, rb.nq:])
+        worst = max(worst, S.rel_err(ta, tb), S.rel_err(ka.getAccelerations(), kb.getAccelerations()), S.rel_err(ka.debug(6), kb.debug(6)))
+        assert worst < tol, (sub, worst)
+        X = np.stack([M.step(rb, X[b], ka.getAccelerations()[b]) for b in range(B)])
+    kb.shareStream(None)
+    assert np.abs(ta).max() > 1e-3
+    print("targets from the MPC on the device vs through host buffers, biped_legs:", "%.1e" % worst)
+    return worst
+
+
+def create_rc(lib, tab, entry="smpc_id_create_any", B=1, force_size=6, na=None, quad=True):
+    na = tab.nv - 6 if na is None else na
+    keep = [np.ones(na) * 10.0, np.ones(na) * 10.0, -np.ones(na), np.ones(na)]
+    qp = np.ascontiguousarray(np.tile(RT.QUAD, (max(tab.nfeet, 1), 1, 1)))
+    c = simple_mpc.IdSettingsC(0.6, 10.0, 0.01, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0, 1e-3, *[a.ctypes.data for a in keep], 0, 0.0, 0.0, 0.0, 0.0, 0, 0.0, 0.0,
+                               -1.0, -1.0, 0, 0, force_size, qp.ctypes.data if (force_size == 6 and quad) else None)
+    h = C.c_void_p()
+    rc = getattr(lib.L, entry)(C.byref(tab), C.byref(c), B, 0, C.byref(h))
+    msg = lib.L.smpc_last_error().decode()
+    if rc == 0:
+        lib.L.smpc_id_destroy(h)
+    return rc, msg, h
+
+
+def refusal_is_gone(lib, B=3):
+    tab = RT.table("biped_legs")
+    rb = RT.oracle_robot(tab)
+    tau_max, v_max = limits("biped_legs")
+    gk = simple_mpc.KinodynamicsID(RT.model_handler(tab, lib), DT, KINO, tau_max, v_max, batch=B, lib=lib)
+    tau = gk.solve(0.0, np.tile(rb.x_ref[: rb.nq], (B, 1)), np.zeros((B, rb.nv)))
+    assert tau.shape == (B, 12) and np.isfinite(tau).all()
+    d = dims(gk)
+    assert (d["n"], d["m"], d["np"], d["mp"], d["nf"], d["nfw"], d["nmot"]) == (42, 106, 48, 112, 2, 6, 6), d
+    d = dims(make("tree32", lib, 1, oracle=False, **KINO)[2])
+    assert (d["n"], d["m"], d["np"], d["mp"], d["nf"], d["nfw"], d["nmot"]) == (61, 144, 64, 144, 2, 6, 6), d
+    # the raw smpc_id_create keeps its answer
+    L = lib or simple_mpc.default_lib()
+    rc, msg, h = create_rc(L, tab, entry="smpc_id_create")
+    assert rc == _INVALID and "flat feet" in msg and not h.value, (rc, msg)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- CPU tier
+def test_refusal_is_gone(built):
+    """KinodynamicsID on biped_legs through the plain constructor: the parent commit raises here with "flat feet (force size 6) on a run-time
+    joint tree are not built"."""
+    refusal_is_gone(S.emu_lib())
+
+
+@pytest.mark.parametrize("centroidal", [False, True])
+@pytest.mark.parametrize("name", ROBOTS)
+def test_quantities_qp_and_solution(built, name, centroidal):
+    pieces(name, S.emu_lib(), centroidal)
+
+
+@pytest.mark.parametrize("variant", [dict(contact_motion_equality=True), dict(tsid_joint_bounds=True), dict(contact_motion_equality=True, tsid_joint_bounds=True),
+                                     dict(base_reference_as_coded=True)])
+def test_qp_variants(built, variant):
+    pieces("biped_legs", S.emu_lib(), False, **variant)
+    pieces("tree32", S.emu_lib(), True, **variant)
+
+
+@pytest.mark.parametrize("centroidal", [False, True])
+@pytest.mark.parametrize("name", ROBOTS)
+def test_solution_at_fixed_work(built, name, centroidal):
+    """tau, a and the wrenches after 100 iterations from a cold start (admm_tol = -1) against the oracle at 1e-8.  Observed on the emulated
+    tier (tau / a / f): biped_legs 1.1e-9 / 4.1e-10 / 1.3e-9 and 2.9e-10 / 1.3e-10 / 4.3e-10, tree32 8.8e-11 / 7.9e-11 / 4.5e-11 and 5.1e-11 /
+    2.6e-11 / 9.5e-12.  The bar rests on the refinement step of the solver's linear solve: with the explicit K^-1 alone these robots, which have
+    not converged after 100 iterations, end 5e-9 .. 3e-6 from the oracle."""
+    pieces(name, S.emu_lib(), centroidal, solution=True)
+
+
+@pytest.mark.parametrize("name", ROBOTS)
+def test_warm_started_ticks(built, name):
+    standing_loop(name, S.emu_lib(), 20, 1e-6, **KINO)
+
+
+@pytest.mark.parametrize("name,ticks", [("biped_legs", 40), ("tree32", 20)])
+def test_default_stopping_rule(built, name, ticks):
+    standing_loop(name, S.emu_lib(), ticks, 1e-4, resid_bars=True, admm_iters=400, admm_tol=1e-7, **dict(KINO, contact_motion_equality=True))
+
+
+@pytest.mark.parametrize("centroidal", [False, True])
+@pytest.mark.parametrize("equality", [False, True])
+def test_contact_quad_acceptance_on_biped_legs(built, equality, centroidal):
+    """The contactQuad acceptance loops of the reference (tests/inverse-dynamics/kinodynamics-id.cpp:192-236, centroidal-id.cpp:202-247) on the
+    product: from x_ref, integrated with the product's own accelerations, the feet stay at rest (linear velocity <= 1e-2, angular <= 1e-1 at every
+    tick), torques, joint velocities and positions stay inside their limits, and the feet carry the robot at the end."""
+    lib = S.emu_lib()
+    rb, _, gk = make("biped_legs", lib, 1, admm_iters=400, admm_tol=1e-7, oracle=False, centroidal=centroidal,
+                     **dict(KINO, contact_motion_equality=equality))
+    tau_max, v_max = limits("biped_legs")
+    x = rb.x_ref.copy()
+    vl = va = 0.0
+    for i in range(300):
+        tau = gk.solve(0.0, x[: rb.nq], x[rb.nq:])
+        x = M.step(rb, x, gk.getAccelerations())
+        vf = O.id_quantities6(rb, x)["vfoot"].reshape(2, 6)
+        vl, va = max(vl, np.linalg.norm(vf[:, :3], axis=1).max()), max(va, np.linalg.norm(vf[:, 3:], axis=1).max())
+        assert np.linalg.norm(vf[:, :3], axis=1).max() <= 1e-2 and np.linalg.norm(vf[:, 3:], axis=1).max() <= 1e-1, i
+        assert np.all(np.abs(tau) <= tau_max + 1e-6) and np.all(np.abs(x[rb.nq + 6:]) <= v_max + 1e-9), i
+        assert np.all(x[7: rb.nq] <= rb.q_hi + 1e-9) and np.all(x[7: rb.nq] >= rb.q_lo - 1e-9), i
+    fz = gk.getContactForces().reshape(2, 6)[:, 2].sum()
+    print("acceptance", "equality" if equality else "cost", "centroidal" if centroidal else "kinodynamics",
+          "foot velocity lin %.1e ang %.1e" % (vl, va), "sum f_z / (m g) = %.4f" % (fz / (rb.mass * 9.81)), "residual %.1e" % gk.resid[0])
+    assert abs(fz - rb.mass * 9.81) < 0.05 * rb.mass * 9.81
+
+
+@pytest.mark.parametrize("centroidal", [False, True])
+def test_run_time_engine_against_templated_engine(built, centroidal):
+    """Quantities and QP data at 1e-11, torques after 100 cold iterations at 1e-8.  Observed on the emulated tier: 7.8e-16 / 7.8e-16 / 2.0e-12
+    (KinodynamicsID), 7.8e-16 / 7.8e-16 / 1.4e-11 (CentroidalID)."""
+    w = rt_vs_templated(S.emu_lib(), centroidal)
+    assert w["quant"] < 1e-11 and w["qp"] < 1e-11 and w["tau"] < 1e-8, w
+
+
+def test_targets_from_run_time_centroidal_mpc(built):
+    resident_targets(S.emu_lib())
+
+
+def test_admission(built):
+    """Through smpc_id_create_any: a refused table names its field, *out stays NULL, and every robot smpc_id_create serves still constructs."""
+    lib = S.emu_lib()
+    bad = RobotModelC.from_buffer_copy(RT.table("biped_legs"))
+    bad.parent[5] = 7
+    rc, msg, h = create_rc(lib, bad)
+    assert rc == _INVALID and "parent[5]" in msg and not h.value, (rc, msg)
+    bad = RobotModelC.from_buffer_copy(RT.table("quad_arm"))
+    rc, msg, h = create_rc(lib, bad)  # 4 feet with force_size 6
+    assert rc == _INVALID and "nfeet = 4" in msg and "2 flat feet" in msg and not h.value, (rc, msg)
+    bad = RobotModelC.from_buffer_copy(RT.table("biped_legs"))
+    bad.njoints = 1000
+    rc, msg, h = create_rc(lib, bad)
+    assert rc == _INVALID and "njoints" in msg and not h.value, (rc, msg)
+    rc, msg, h = create_rc(lib, RT.table("biped_legs"), quad=False)
+    assert rc == _INVALID and "quad_contact_points" in msg and not h.value, (rc, msg)
+    tau_max, v_max = limits("biped_legs")
+    with pytest.raises(RuntimeError, match="nv - 6 entries"):
+        simple_mpc.KinodynamicsID(RT.model_handler(RT.table("biped_legs"), lib), DT, KINO, tau_max[:-1], v_max, batch=1, lib=lib)
+    # the two built shapes, quad_arm and the new ground construct through the new entry
+    assert create_rc(lib, RT.table("go2_like"), force_size=3)[0] == 0
+    assert create_rc(lib, RT.table("talos_like"))[0] == 0
+    assert create_rc(lib, RT.table("quad_arm"), force_size=3)[0] == 0
+    assert create_rc(lib, RT.table("biped_legs"))[0] == 0
+    # ... and point feet keep their refusals there
+    bad = RobotModelC.from_buffer_copy(RT.table("quad_arm"))
+    bad.nfeet = 3
+    rc, msg, h = create_rc(lib, bad, force_size=3)
+    assert rc == _INVALID and "nfeet = 3" in msg and not h.value, (rc, msg)
