@@ -35,7 +35,8 @@ typedef struct smpc_robot_model
   int nv;      /* 6 + (njoints-1) */
   int parent[SMPC_MAX_JOINTS]; /* -1 for joint 0 */
   int jtype[SMPC_MAX_JOINTS];  /* 0 free-flyer, 1 RX, 2 RY, 3 RZ */
-  double jp_R[SMPC_MAX_JOINTS][9]; /* joint placement in parent joint frame, row-major */
+  double jp_R[SMPC_MAX_JOINTS][9]; /* joint placement in parent joint frame, row-major; any rotation (R^T R = I to 1e-9, det > 0):
+                                      a table with another matrix here is refused where tables are validated */
   double jp_p[SMPC_MAX_JOINTS][3];
   double mass[SMPC_MAX_JOINTS];
   double com[SMPC_MAX_JOINTS][3];

@@ -47,6 +47,17 @@ namespace smpc
     {
       if (!finite(rm->jp_R[j], 9))
         return say("jp_R[%d] is not finite", j);
+      {
+        // a placement is a rotation: R^T R = I (1e-9, the tolerance of total_mass below) and det R > 0
+        const double * R = rm->jp_R[j];
+        double dev = 0.0;
+        for (int a = 0; a < 3; a++)
+          for (int c = 0; c < 3; c++)
+            dev = std::fmax(dev, std::fabs(R[a] * R[c] + R[3 + a] * R[3 + c] + R[6 + a] * R[6 + c] - (a == c ? 1.0 : 0.0)));
+        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (!(dev <= 1e-9) || !(det > 0.0))
+          return say("jp_R[%d] is not a rotation (max |R^T R - I| = %.3g, det = %.3g)", j, dev, det);
+      }
       if (!finite(rm->jp_p[j], 3))
         return say("jp_p[%d] is not finite", j);
       if (!std::isfinite(rm->mass[j]) || !(rm->mass[j] > 0.0))

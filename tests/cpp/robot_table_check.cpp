@@ -3,6 +3,7 @@
 // tests/test_robot_table_host.py; every table lives in a heap block of exactly sizeof(smpc_robot_model) bytes, so that a read past the
 // struct -- a table that claims 33 joints, a foot on joint 1000 -- is a sanitizer report and not a silent pass.
 #include "smpc_robot_check.h"
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -120,6 +121,9 @@ int main()
   refused(19, 4, [&](smpc_robot_model & m) { m.mass[2] = -1.0; }, "mass[2]");
   refused(19, 4, [&](smpc_robot_model & m) { m.mass[2] = inf; }, "mass[2]");
   refused(19, 4, [&](smpc_robot_model & m) { m.jp_R[4][8] = nan; }, "jp_R[4]");
+  refused(19, 4, [](smpc_robot_model & m) { for (int i = 0; i < 9; i++) m.jp_R[7][i] *= 1.001; }, "jp_R[7] is not a rotation");  // scaled
+  refused(19, 4, [](smpc_robot_model & m) { m.jp_R[11][8] = -1.0; }, "jp_R[11] is not a rotation");  // a reflection: orthonormal, det = -1
+  refused(19, 4, [](smpc_robot_model & m) { m.jp_R[3][1] = 1e-8; }, "jp_R[3] is not a rotation");  // sheared beyond 1e-9
   refused(19, 4, [&](smpc_robot_model & m) { m.jp_p[18][0] = inf; }, "jp_p[18]");
   refused(19, 4, [&](smpc_robot_model & m) { m.com[1][1] = -inf; }, "com[1]");
   refused(19, 4, [&](smpc_robot_model & m) { m.inertia[9][5] = nan; }, "inertia[9]");
@@ -136,6 +140,17 @@ int main()
   refused(19, 4, [](smpc_robot_model & m) { m.foot_joint[3] = 1000; }, "foot_joint[3]");
   refused(19, 4, [](smpc_robot_model & m) { m.nfeet = SMPC_MAX_FEET + 1; }, "nfeet");
   refused(19, 4, [](smpc_robot_model & m) { m.nfeet = 0; }, "nfeet");
+  // a dense rotation that is orthonormal to rounding passes (X by 0.7 rad times Z by -2.1 rad), and so does a deviation below 1e-9
+  {
+    smpc_robot_model * m = make(19, 4);
+    const double c1 = std::cos(0.7), s1 = std::sin(0.7), c2 = std::cos(-2.1), s2 = std::sin(-2.1);
+    const double R[9] = {c2, -s2, 0.0, c1 * s2, c1 * c2, -s1, s1 * s2, s1 * c2, c1};
+    std::memcpy(m->jp_R[9], R, sizeof(R));
+    CHECK(smpc::robot_table_error(m).empty());
+    m->jp_R[9][2] = 1e-10;
+    CHECK(smpc::robot_table_error(m).empty());
+    std::free(m);
+  }
   // what lies past the table's own joints / feet is not looked at
   {
     smpc_robot_model * m = make(14, 2);

@@ -1,5 +1,6 @@
 """Shared construction of (oracle MPC, product MPC) pairs on the Go2 kinodynamics settings of record
 (reference examples/go2_kinodynamics.py:30-139).  TEST INFRASTRUCTURE."""
+import contextlib
 import os
 import sys
 
@@ -48,8 +49,48 @@ def xcheck_lib():
     return _xcheck
 
 
-def make_product(batch, max_iters=1, lib=None, horizon=50, settings_override=None, mpc_override=None, device_id=0):
-    rb = O.Robot("go2_like")
+_stand_in = {}  # built-in name -> table name of robot_tables that the factories build in its place (robots(); empty outside of it)
+
+
+def _robot_name(robot, default):
+    return robot if robot is not None else _stand_in.get(default, default)
+
+
+def _oracle_robot(robot, default):
+    """The oracle's robot of a factory: the built-in table `default` unless robot= (or robots()) names a table of robot_tables."""
+    name = _robot_name(robot, default)
+    if name == default:
+        return O.Robot(name)
+    import robot_tables as RT
+
+    return RT.oracle_robot(RT.table(name))
+
+
+def _product_robot(robot, default, lib):
+    """The product's model of a factory: load_robot(default), or robot_from_table of the table that robot= names."""
+    name = _robot_name(robot, default)
+    if name == default:
+        return simple_mpc.load_robot(name, lib)
+    import robot_tables as RT
+
+    return simple_mpc.robot_from_table(RT.table(name))
+
+
+@contextlib.contextmanager
+def robots(**stand_in):
+    """Inside the block every factory of this file called without robot= builds the named table in place of its built-in robot, oracle and
+    product alike: robots(go2_like="go2_like_rf").  For running a test body that calls the factories itself on another table."""
+    old = dict(_stand_in)
+    _stand_in.update(stand_in)
+    try:
+        yield
+    finally:
+        _stand_in.clear()
+        _stand_in.update(old)
+
+
+def make_product(batch, max_iters=1, lib=None, horizon=50, settings_override=None, mpc_override=None, device_id=0, robot=None):
+    rb = _oracle_robot(robot, "go2_like")
     s = O.go2_kino_settings(rb)
     if settings_override:
         s.update(settings_override)
@@ -57,7 +98,7 @@ def make_product(batch, max_iters=1, lib=None, horizon=50, settings_override=Non
     ms["T"] = horizon
     if mpc_override:
         ms.update(mpc_override)
-    mh = simple_mpc.RobotModelHandler(simple_mpc.load_robot("go2_like", lib), "standing", "root_joint")
+    mh = simple_mpc.RobotModelHandler(_product_robot(robot, "go2_like", lib), "standing", "root_joint")
     for n in FEET:
         mh.addPointFoot(n, "root_joint")
     ocp = simple_mpc.KinodynamicsOCP(s, mh)
@@ -67,8 +108,8 @@ def make_product(batch, max_iters=1, lib=None, horizon=50, settings_override=Non
     return gm, rb, s, ms
 
 
-def make_oracle(batch, max_iters=1, horizon=50, settings_override=None, mpc_override=None):
-    rb = O.Robot("go2_like")
+def make_oracle(batch, max_iters=1, horizon=50, settings_override=None, mpc_override=None, robot=None):
+    rb = _oracle_robot(robot, "go2_like")
     s = O.go2_kino_settings(rb)
     if settings_override:
         s.update(settings_override)
@@ -103,9 +144,9 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / max(1.0, np.abs(a).max()))
 
 
-def make_cent_product(batch, max_iters=1, lib=None, horizon=50, settings_override=None, mpc_override=None, device_id=0):
+def make_cent_product(batch, max_iters=1, lib=None, horizon=50, settings_override=None, mpc_override=None, device_id=0, robot=None):
     """simple_mpc.BatchedMPC over a CentroidalOCP with the centroidal settings of record (oracle_lib.go2_centroidal_settings)."""
-    rb = O.Robot("go2_like")
+    rb = _oracle_robot(robot, "go2_like")
     s = O.go2_centroidal_settings(rb)
     if settings_override:
         s.update(settings_override)
@@ -113,7 +154,7 @@ def make_cent_product(batch, max_iters=1, lib=None, horizon=50, settings_overrid
     ms["T"] = horizon
     if mpc_override:
         ms.update(mpc_override)
-    mh = simple_mpc.RobotModelHandler(simple_mpc.load_robot("go2_like", lib), "standing", "root_joint")
+    mh = simple_mpc.RobotModelHandler(_product_robot(robot, "go2_like", lib), "standing", "root_joint")
     for n in FEET:
         mh.addPointFoot(n, "root_joint")
     ocp = simple_mpc.CentroidalOCP(s, mh)
@@ -123,8 +164,8 @@ def make_cent_product(batch, max_iters=1, lib=None, horizon=50, settings_overrid
     return gm, rb, s, ms
 
 
-def make_cent_oracle(batch, max_iters=1, horizon=50, settings_override=None, mpc_override=None):
-    rb = O.Robot("go2_like")
+def make_cent_oracle(batch, max_iters=1, horizon=50, settings_override=None, mpc_override=None, robot=None):
+    rb = _oracle_robot(robot, "go2_like")
     s = O.go2_centroidal_settings(rb)
     if settings_override:
         s.update(settings_override)
@@ -148,9 +189,9 @@ def make_cent_pair(batch, max_iters=1, lib=None, horizon=50, walk=(0.2, 0, 0, 0,
     return om, gm, rb
 
 
-def make_full_product(batch, max_iters=1, lib=None, horizon=50, settings_override=None, mpc_override=None, device_id=0):
+def make_full_product(batch, max_iters=1, lib=None, horizon=50, settings_override=None, mpc_override=None, device_id=0, robot=None):
     """simple_mpc.BatchedMPC over a FullDynamicsOCP with the Go2 settings of record (oracle_lib.go2_full_settings)."""
-    rb = O.Robot("go2_like")
+    rb = _oracle_robot(robot, "go2_like")
     s = O.go2_full_settings(rb)
     s.update(dict(force_size=3, mu=0.8, Lfoot=0.01, Wfoot=0.01, force_cone=False, land_cstr=False))
     if settings_override:
@@ -159,7 +200,7 @@ def make_full_product(batch, max_iters=1, lib=None, horizon=50, settings_overrid
     ms["T"] = horizon
     if mpc_override:
         ms.update(mpc_override)
-    mh = simple_mpc.RobotModelHandler(simple_mpc.load_robot("go2_like", lib), "standing", "root_joint")
+    mh = simple_mpc.RobotModelHandler(_product_robot(robot, "go2_like", lib), "standing", "root_joint")
     for n in FEET:
         mh.addPointFoot(n, "root_joint")
     ocp = simple_mpc.FullDynamicsOCP(s, mh)
@@ -169,8 +210,8 @@ def make_full_product(batch, max_iters=1, lib=None, horizon=50, settings_overrid
     return gm, rb, s, ms
 
 
-def make_full_oracle(batch, max_iters=1, horizon=50, settings_override=None, mpc_override=None, walk=(0.2, 0, 0, 0, 0, 0)):
-    rb = O.Robot("go2_like")
+def make_full_oracle(batch, max_iters=1, horizon=50, settings_override=None, mpc_override=None, walk=(0.2, 0, 0, 0, 0, 0), robot=None):
+    rb = _oracle_robot(robot, "go2_like")
     s = O.go2_full_settings(rb)
     if settings_override:
         s.update(settings_override)
@@ -198,9 +239,9 @@ TALOS_FEET = ["left_sole_link", "right_sole_link"]
 TALOS_QUAD = np.array([[0.1, 0.075, 0], [-0.1, 0.075, 0], [-0.1, -0.075, 0], [0.1, -0.075, 0]])
 
 
-def make_talos_product(batch, max_iters=1, lib=None, horizon=100, settings_override=None, mpc_override=None, device_id=0):
+def make_talos_product(batch, max_iters=1, lib=None, horizon=100, settings_override=None, mpc_override=None, device_id=0, robot=None):
     """simple_mpc.BatchedMPC over the Talos full-dynamics OCP (6-D feet, wrench cones; oracle_lib.talos_full_settings)."""
-    rb = O.Robot("talos_like")
+    rb = _oracle_robot(robot, "talos_like")
     s = O.talos_full_settings(rb)
     if settings_override:
         s.update(settings_override)
@@ -208,7 +249,7 @@ def make_talos_product(batch, max_iters=1, lib=None, horizon=100, settings_overr
     ms["T"] = horizon
     if mpc_override:
         ms.update(mpc_override)
-    mh = simple_mpc.RobotModelHandler(simple_mpc.load_robot("talos_like", lib), "standing", "root_joint")
+    mh = simple_mpc.RobotModelHandler(_product_robot(robot, "talos_like", lib), "standing", "root_joint")
     for n in TALOS_FEET:
         mh.addQuadFoot(n, "root_joint", TALOS_QUAD)
     ocp = simple_mpc.FullDynamicsOCP(s, mh)
@@ -218,8 +259,8 @@ def make_talos_product(batch, max_iters=1, lib=None, horizon=100, settings_overr
     return gm, rb, s, ms
 
 
-def make_talos_pair(batch, max_iters=1, lib=None, horizon=100, walk=(0.1, 0, 0, 0, 0, 0), cycle=None, **kw):
-    rb = O.Robot("talos_like")
+def make_talos_pair(batch, max_iters=1, lib=None, horizon=100, walk=(0.1, 0, 0, 0, 0, 0), cycle=None, robot=None, **kw):
+    rb = _oracle_robot(robot, "talos_like")
     s = O.talos_full_settings(rb)
     if kw.get("settings_override"):
         s.update(kw["settings_override"])
@@ -228,7 +269,7 @@ def make_talos_pair(batch, max_iters=1, lib=None, horizon=100, walk=(0.1, 0, 0, 
     if kw.get("mpc_override"):
         ms.update(kw["mpc_override"])
     om = O.OracleFullMPC(O.Full(rb, s), ms, batch)
-    gm, _, _, _ = make_talos_product(batch, max_iters, lib, horizon, **kw)
+    gm, _, _, _ = make_talos_product(batch, max_iters, lib, horizon, robot=robot, **kw)
     cs = O.walk_cycle() if cycle is None else cycle
     for m in (om, gm):
         m.generateCycleHorizon(cs)
@@ -257,10 +298,10 @@ def alphas_agree(om, gm, rtol=1e-8):
     return True
 
 
-def make_talos_kino_product(batch, max_iters=1, lib=None, horizon=100, settings_override=None, mpc_override=None, device_id=0):
+def make_talos_kino_product(batch, max_iters=1, lib=None, horizon=100, settings_override=None, mpc_override=None, device_id=0, robot=None):
     """simple_mpc.BatchedMPC over the Talos KINODYNAMICS OCP with 6-D feet (oracle_lib.talos_kino_settings: the weights of the reference's
     examples/talos_kinodynamics.py, force_cone as in its tests/test_utils.cpp)."""
-    rb = O.Robot("talos_like")
+    rb = _oracle_robot(robot, "talos_like")
     s = O.talos_kino_settings(rb)
     if settings_override:
         s.update(settings_override)
@@ -268,7 +309,7 @@ def make_talos_kino_product(batch, max_iters=1, lib=None, horizon=100, settings_
     ms["T"] = horizon
     if mpc_override:
         ms.update(mpc_override)
-    mh = simple_mpc.RobotModelHandler(simple_mpc.load_robot("talos_like", lib), "standing", "root_joint")
+    mh = simple_mpc.RobotModelHandler(_product_robot(robot, "talos_like", lib), "standing", "root_joint")
     for n in TALOS_FEET:
         mh.addQuadFoot(n, "root_joint", TALOS_QUAD)
     ocp = simple_mpc.KinodynamicsOCP(s, mh)
@@ -278,8 +319,8 @@ def make_talos_kino_product(batch, max_iters=1, lib=None, horizon=100, settings_
     return gm, rb, s, ms
 
 
-def make_talos_kino_pair(batch, max_iters=1, lib=None, horizon=100, walk=(0.1, 0, 0, 0, 0, 0), cycle=None, **kw):
-    rb = O.Robot("talos_like")
+def make_talos_kino_pair(batch, max_iters=1, lib=None, horizon=100, walk=(0.1, 0, 0, 0, 0, 0), cycle=None, robot=None, **kw):
+    rb = _oracle_robot(robot, "talos_like")
     s = O.talos_kino_settings(rb)
     if kw.get("settings_override"):
         s.update(kw["settings_override"])
@@ -291,7 +332,7 @@ def make_talos_kino_pair(batch, max_iters=1, lib=None, horizon=100, walk=(0.1, 0
         O.lib().orc_set_terminal_constraint(1)
     om = O.OracleMPC(O.Kino(rb, s), ms, batch)
     O.lib().orc_set_terminal_constraint(0)
-    gm, _, _, _ = make_talos_kino_product(batch, max_iters, lib, horizon, **kw)
+    gm, _, _, _ = make_talos_kino_product(batch, max_iters, lib, horizon, robot=robot, **kw)
     cs = O.walk_cycle() if cycle is None else cycle
     for m in (om, gm):
         m.generateCycleHorizon(cs)
@@ -299,9 +340,9 @@ def make_talos_kino_pair(batch, max_iters=1, lib=None, horizon=100, walk=(0.1, 0
     return om, gm, rb
 
 
-def make_talos_cent_product(batch, max_iters=1, lib=None, horizon=100, settings_override=None, mpc_override=None, device_id=0):
+def make_talos_cent_product(batch, max_iters=1, lib=None, horizon=100, settings_override=None, mpc_override=None, device_id=0, robot=None):
     """simple_mpc.BatchedMPC over the Talos CENTROIDAL OCP with 6-D feet (oracle_lib.talos_centroidal_settings: examples/talos_centroidal.py)."""
-    rb = O.Robot("talos_like")
+    rb = _oracle_robot(robot, "talos_like")
     s = O.talos_centroidal_settings(rb)
     if settings_override:
         s.update(settings_override)
@@ -309,7 +350,7 @@ def make_talos_cent_product(batch, max_iters=1, lib=None, horizon=100, settings_
     ms["T"] = horizon
     if mpc_override:
         ms.update(mpc_override)
-    mh = simple_mpc.RobotModelHandler(simple_mpc.load_robot("talos_like", lib), "standing", "root_joint")
+    mh = simple_mpc.RobotModelHandler(_product_robot(robot, "talos_like", lib), "standing", "root_joint")
     for n in TALOS_FEET:
         mh.addQuadFoot(n, "root_joint", TALOS_QUAD)
     ocp = simple_mpc.CentroidalOCP(s, mh)
@@ -319,8 +360,8 @@ def make_talos_cent_product(batch, max_iters=1, lib=None, horizon=100, settings_
     return gm, rb, s, ms
 
 
-def make_talos_cent_pair(batch, max_iters=1, lib=None, horizon=100, walk=(0.1, 0, 0, 0, 0, 0), cycle=None, **kw):
-    rb = O.Robot("talos_like")
+def make_talos_cent_pair(batch, max_iters=1, lib=None, horizon=100, walk=(0.1, 0, 0, 0, 0, 0), cycle=None, robot=None, **kw):
+    rb = _oracle_robot(robot, "talos_like")
     s = O.talos_centroidal_settings(rb)
     if kw.get("settings_override"):
         s.update(kw["settings_override"])
@@ -329,7 +370,7 @@ def make_talos_cent_pair(batch, max_iters=1, lib=None, horizon=100, walk=(0.1, 0
     if kw.get("mpc_override"):
         ms.update(kw["mpc_override"])
     om = O.OracleCentMPC(O.Cent(rb, s), ms, batch)
-    gm, _, _, _ = make_talos_cent_product(batch, max_iters, lib, horizon, **kw)
+    gm, _, _, _ = make_talos_cent_product(batch, max_iters, lib, horizon, robot=robot, **kw)
     cs = O.walk_cycle() if cycle is None else cycle
     for m in (om, gm):
         m.generateCycleHorizon(cs)

@@ -111,17 +111,162 @@ def tree32():
     return _finish(m, "tree32", 32)
 
 
+def _axis_rotation(axis, phi):
+    """Rotation by phi about coordinate axis 1 / 2 / 3 (the jtype of a revolute joint)."""
+    c, s = np.cos(phi), np.sin(phi)
+    i, j, k = axis - 1, axis % 3, (axis + 1) % 3
+    R = np.zeros((3, 3))
+    R[i, i], R[j, j], R[k, k], R[j, k], R[k, j] = 1.0, c, c, -s, s
+    return R
+
+
+_SYM = ((0, 0), (0, 1), (1, 1), (0, 2), (1, 2), (2, 2))  # the inertia's order: xx xy yy xz yz zz
+
+
+def reframe(tab, seed):
+    """The same robot with the frame of every joint turned about the joint's own axis: G_j = rot(jtype[j], phi_j), phi_j uniform in
+    [-pi, pi], G = I on the base and on every foot joint.  A rotation about the axis commutes with the joint's motion, so q, v and tau keep
+    their meaning, and with G = I on the feet so do foot frames, local contact forces and wrench cones:
+
+        jp_R' = G_parent^T jp_R G_j     jp_p' = G_parent^T jp_p     com' = G_j^T com     I' = G_j^T I G_j
+
+    foot_p, foot_ref_p, q_ref, q_lo, q_hi and the masses are untouched.  jp_R' is a dense rotation on every joint but the base: a seed
+    that leaves one within 0.1 of the identity is refused."""
+    rng = np.random.default_rng(seed)
+    nj = tab.njoints
+    feet = {tab.foot_joint[f] for f in range(tab.nfeet)}
+    phi = rng.uniform(-np.pi, np.pi, nj)
+    G = [np.eye(3) if j == 0 or j in feet else _axis_rotation(tab.jtype[j], phi[j]) for j in range(nj)]
+    m = RobotModelC.from_buffer_copy(tab)
+    for j in range(1, nj):
+        Gp, Gj = G[tab.parent[j]], G[j]
+        R = Gp.T @ np.array(tab.jp_R[j][:]).reshape(3, 3) @ Gj
+        assert np.abs(R - np.eye(3)).max() > 0.1, ("seed %d leaves joint %d near the identity" % (seed, j), R)
+        inertia = np.zeros((3, 3))
+        for i, (r, c) in enumerate(_SYM):
+            inertia[r, c] = inertia[c, r] = tab.inertia[j][i]
+        inertia = Gj.T @ inertia @ Gj
+        p, com = Gp.T @ np.array(tab.jp_p[j][:]), Gj.T @ np.array(tab.com[j][:])
+        for i in range(9):
+            m.jp_R[j][i] = R.flat[i]
+        for i in range(3):
+            m.jp_p[j][i], m.com[j][i] = p[i], com[i]
+        for i, (r, c) in enumerate(_SYM):
+            m.inertia[j][i] = inertia[r, c]
+    m.name = (tab.name.decode() + "_rf").encode()
+    return m
+
+
+class Renumbering:
+    """new_of_old[j]: the number that joint j of the original table has in the renumbered one.  Maps states, velocity-space vectors,
+    torques and the velocity-space columns of matrices between the two numberings."""
+
+    def __init__(self, new_of_old):
+        self.new_of_old = np.asarray(new_of_old)
+        nj = len(self.new_of_old)
+        self.a = self.new_of_old[1:] - 1  # actuated joints: old position -> new position
+        self.v = np.r_[np.arange(6), 6 + self.a]  # w_old = w_new[..., v]
+        self.x = np.r_[np.arange(7), 7 + self.a, nj + 6 + self.v]
+
+    def _to_new(self, old, idx):
+        new = np.empty_like(old)
+        new[..., idx] = old
+        return new
+
+    def state(self, X_old):
+        return self._to_new(np.asarray(X_old), self.x)
+
+    def velocity(self, v_old):
+        return self._to_new(np.asarray(v_old), self.v)
+
+    def torque(self, tau_old):
+        return self._to_new(np.asarray(tau_old), self.a)
+
+    def velocity_back(self, v_new):
+        return np.asarray(v_new)[..., self.v]
+
+    def torque_back(self, tau_new):
+        return np.asarray(tau_new)[..., self.a]
+
+    def state_back(self, X_new):
+        return np.asarray(X_new)[..., self.x]
+
+    def columns_back(self, M_new):
+        """[.., nv] of the renumbered robot -> columns in the original order (J, Ag); apply twice (with .T) for M."""
+        return np.asarray(M_new)[..., self.v]
+
+
+def renumber(tab, seed):
+    """(table, new_of_old): the same robot with its joints in another topological order, drawn at random (joint 0 stays, every parent
+    comes before its children)."""
+    rng = np.random.default_rng(seed)
+    nj = tab.njoints
+    order, ready = [0], [j for j in range(1, nj) if tab.parent[j] == 0]
+    while ready:
+        j = ready.pop(int(rng.integers(len(ready))))
+        order.append(j)
+        ready += [k for k in range(1, nj) if tab.parent[k] == j]
+    assert sorted(order) == list(range(nj))
+    new_of_old = np.empty(nj, int)
+    new_of_old[order] = np.arange(nj)
+    assert (new_of_old != np.arange(nj)).sum() > nj // 2, ("seed %d leaves most joints in place" % seed, new_of_old)
+    m = RobotModelC.from_buffer_copy(tab)
+    for new, old in enumerate(order):
+        _copy_joint(m, new, tab, old, -1 if old == 0 else int(new_of_old[tab.parent[old]]))
+    for f in range(tab.nfeet):
+        m.foot_joint[f] = int(new_of_old[tab.foot_joint[f]])
+    name = tab.name.decode()
+    m.name = ((name[:-3] if name.endswith("_rf") else name) + "_rn").encode()
+    return m, new_of_old
+
+
+def _tree32p():
+    import test_id_any_robot as T  # (the 32-joint point-foot table lives with the tests that introduced it)
+
+    return T.table("tree32p")
+
+
 MAKERS = {"quad_arm": quad_arm, "biped_legs": biped_legs, "tree32": tree32}
+# <name>_rf: reframe(table(name)); <name>_rn: the re-framed table renumbered.  Seeds: the first that pass the helpers' own assertions.
+REFRAME_SEED = {"quad_arm": 1, "biped_legs": 1, "tree32": 1, "tree32p": 1, "go2_like": 1, "talos_like": 1}
+RENUMBER_SEED = {"quad_arm": 1, "biped_legs": 2, "tree32": 1, "tree32p": 1}
+REFRAMED = [n + "_rf" for n in REFRAME_SEED]
+RENUMBERED = [n + "_rn" for n in RENUMBER_SEED]
 FEET = {4: ["FL_foot", "FR_foot", "RL_foot", "RR_foot"], 2: ["left_sole_link", "right_sole_link"]}
 QUAD = np.array([[0.1, 0.075, 0], [-0.1, 0.075, 0], [-0.1, -0.075, 0], [0.1, -0.075, 0]])
-_tables = {}
+_tables, _renumberings = {}, {}
+
+
+def base_name(name):
+    """("quad_arm", "rn") of "quad_arm_rn"; (name, "") of a table that is not derived by reframe / renumber."""
+    return (name[:-3], name[-2:]) if name[-3:] in ("_rf", "_rn") else (name, "")
 
 
 def table(name):
     """One table per robot for the whole session (never modified: the tests that need a bad table copy it)."""
     if name not in _tables:
-        _tables[name] = MAKERS[name]() if name in MAKERS else _builtin(name)
+        base, kind = base_name(name)
+        if kind == "rf":
+            _tables[name] = reframe(_tree32p() if base == "tree32p" else table(base), REFRAME_SEED[base])
+        elif kind == "rn":
+            _tables[name], new_of_old = renumber(table(base + "_rf"), RENUMBER_SEED[base])
+            _renumberings[name] = Renumbering(new_of_old)
+        else:
+            _tables[name] = MAKERS[name]() if name in MAKERS else _builtin(name)
     return _tables[name]
+
+
+def register(name, tab):
+    """A table of a test's own making under a name, for the helpers that take names."""
+    assert name not in _tables or _tables[name] is tab, name
+    _tables[name] = tab
+    return tab
+
+
+def renumbering(name):
+    """The Renumbering of a <name>_rn table against <name> (and <name>_rf)."""
+    table(name)
+    return _renumberings[name]
 
 
 def oracle_robot(tab):

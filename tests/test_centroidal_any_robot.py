@@ -261,6 +261,8 @@ def test_invalid_tables_are_refused_by_field(lib):
         ("biped_legs", set_("foot_joint", 1, 13), r"foot_joint\[1\]"),
         ("tree32", lambda t: t.com[20].__setitem__(1, float("inf")), r"com\[20\]"),
         ("quad_arm", lambda t: t.jp_p[18].__setitem__(2, float("nan")), r"jp_p\[18\]"),
+        ("quad_arm", lambda t: [t.jp_R[14].__setitem__(i, 1.001 * t.jp_R[14][i]) for i in range(9)], r"jp_R\[14\] is not a rotation"),  # scaled
+        ("tree32", lambda t: t.jp_R[30].__setitem__(8, -t.jp_R[30][8]), r"jp_R\[30\] is not a rotation"),  # a reflection
     ]
     for name, edit, pat in cases:
         rc, msg = _create(lib, _bad(name, edit))

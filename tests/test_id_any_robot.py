@@ -168,16 +168,16 @@ def closed_loop(name, lib, n_steps, tol, B=2, **solver):
     return worst
 
 
-def rt_vs_templated(lib, B=3):
-    """go2_like through the debug switch against IdEngine<Go2> on the same inputs."""
+def rt_vs_templated(lib, B=3, name="go2_like"):
+    """go2_like (or a table of its shape) through the debug switch against IdEngine<Go2> on the same inputs."""
     worst = {}
     for centroidal in (False, True):
-        rb, ok, grt = make("go2_like", lib, B, centroidal=centroidal, **(CALL if centroidal else ALL))
-        mh = RT.model_handler(table("go2_like"), lib)
+        rb, ok, grt = make(name, lib, B, centroidal=centroidal, **(CALL if centroidal else ALL))
+        mh = RT.model_handler(table(name), lib)
         tau_max, v_max = limits(rb)
         cls, keys = (simple_mpc.CentroidalID, CKEYS) if centroidal else (simple_mpc.KinodynamicsID, KEYS)
         gt = cls(mh, DT, {k: ok_s for k, ok_s in dict(CALL if centroidal else ALL).items() if k in keys}, tau_max, v_max, batch=B, lib=lib, admm_iters=100, admm_tol=-1.0)
-        X = RT.random_states(table("go2_like"), B, seed=24, tilt=0.3, spread=0.5)
+        X = RT.random_states(table(name), B, seed=24, tilt=0.3, spread=0.5)
         ta = gt.solve(0.0, X[:, : rb.nq], X[:, rb.nq:])
         tb = grt.solve(0.0, X[:, : rb.nq], X[:, rb.nq:])
         for w in range(12):
@@ -187,7 +187,7 @@ def rt_vs_templated(lib, B=3):
             assert np.array_equal(fin, np.abs(b) < 1e19)
             worst[key] = max(worst.get(key, 0.0), S.rel_err(a[fin], b[fin]))
         worst["tau"] = max(worst.get("tau", 0.0), S.rel_err(ta, tb))
-    print("run-time engine vs templated engine, go2_like", {k: "%.1e" % v for k, v in worst.items()})
+    print("run-time engine vs templated engine, %s" % name, {k: "%.1e" % v for k, v in worst.items()})
     assert worst["quant"] < 1e-11 and worst["qp"] < 1e-11 and worst["tau"] < 1e-8, worst
     return worst
 

@@ -36,6 +36,10 @@ _INVALID = -1  # SMPC_ERR_INVALID (include/smpc.h)
 
 def limits(name):
     """Effort / velocity limits in the table's joint order (O.TALOS_EFFORT / O.TALOS_VMAX are indexed by talos_like joint - 1)."""
+    base, kind = RT.base_name(name)
+    if kind:  # re-framed: the same joints; renumbered: the same limits in the new joint order
+        tau, vmax = limits(base)
+        return (RT.renumbering(name).torque(tau), RT.renumbering(name).torque(vmax)) if kind == "rn" else (tau, vmax)
     if name == "talos_like":
         return O.TALOS_EFFORT.copy(), O.TALOS_VMAX.copy()
     if name == "biped_legs":
@@ -187,13 +191,13 @@ def standing_loop(name, lib, n_steps, tol, B=1, resid_bars=False, **solver):
     return worst
 
 
-def rt_vs_templated(lib, centroidal, B=3):
+def rt_vs_templated(lib, centroidal, B=3, name="talos_like"):
     """talos_like through the debug switch (run-time flat-foot engine) against IdEngine<FullTalos> on the same inputs: the random states of the
     point-foot sibling (seed 24); CentroidalID with the targets of the golden fixture (right foot in the air, tracked)."""
-    tab = RT.table("talos_like")
+    tab = RT.table(name)
     sett = CENT if centroidal else KINO
     X = RT.random_states(tab, B, seed=24, tilt=0.3, spread=0.5)
-    rb, _, grt = make("talos_like", lib, B, oracle=False, centroidal=centroidal, **sett)
+    rb, _, grt = make(name, lib, B, oracle=False, centroidal=centroidal, **sett)
     cls = simple_mpc.CentroidalID if centroidal else simple_mpc.KinodynamicsID
     gt = cls(RT.model_handler(tab, lib), DT, sett, O.TALOS_EFFORT, O.TALOS_VMAX, batch=B, lib=lib, admm_iters=100, admm_tol=-1.0)
     assert dims(grt)["np"] == 64 and dims(gt)["n"] == dims(grt)["n"] == 52
@@ -215,7 +219,7 @@ def rt_vs_templated(lib, centroidal, B=3):
         worst[key] = max(worst.get(key, 0.0), S.rel_err(a[fin], b[fin]))
     worst["tau"] = S.rel_err(ta, tb)
     assert np.isfinite(tb).all() and np.abs(tb).max() > 1e-3
-    print("run-time flat-foot engine vs templated engine, talos_like,", "centroidal" if centroidal else "kinodynamics",
+    print("run-time flat-foot engine vs templated engine, %s," % name, "centroidal" if centroidal else "kinodynamics",
           {k: "%.1e" % v for k, v in worst.items()}, "residuals", gt.resid, grt.resid)
     return worst
 
