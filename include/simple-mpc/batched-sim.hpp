@@ -94,6 +94,62 @@ namespace simple_mpc
     void lastDevicePointers(double ** a_device, double ** lambda_device) { check(smpc_robot_sim_get_last(h_, a_device, lambda_device)); }
     smpc_robot_sim * handle() { return h_; }
 
+    // ---- ground plane with unilateral frictional contact detected from the state (smpc_robot_sim_set_ground and the entries after it) ----
+    // fields that are 0 stand for their defaults (mu 0.7, erp 0.2, compliance 1e-8, sweeps 30, one point at the foot frame's origin);
+    // may be called again; nfeet * points_per_foot <= 8
+    void setGround(const smpc_ground_settings & settings)
+    {
+      check(smpc_robot_sim_set_ground(h_, &settings));
+      int d[2];
+      check(smpc_robot_sim_get_ground_dims(h_, d));
+      gp_ = d[0];
+      gn_ = d[1];
+    }
+    int groundPointsPerFoot() const { return gp_; }
+    int groundPoints() const { return gn_; }
+    // one step of the batch on the ground, X [B][nq + nv] updated in place, tau [B][nv - 6] (device); asynchronous on the handle's stream
+    void stepGroundDevice(double * X_device, const double * tau_device, double dt)
+    {
+      if (!(dt > 0.0))
+        throw std::runtime_error("dt must be positive");
+      check(smpc_robot_sim_step_ground_device(h_, X_device, tau_device, dt));
+    }
+    struct GroundDynamics
+    {
+      std::vector<double> v_next, a, lambda, gap; // [n][nv], [n][nv], [n][3 points] (on the robot, world axes), [n][points]
+      std::vector<uint32_t> contact;              // [n] bit per point: positive normal force
+    };
+    // the solve of one ground step on host buffers X [n][nq + nv], tau [n][nv - 6]; n need not be the batch, nothing is advanced
+    GroundDynamics groundDynamics(const std::vector<double> & X, const std::vector<double> & tau, double dt)
+    {
+      const size_t nx = (size_t)(nq_ + nv_), n = X.size() / nx;
+      if (n == 0 || X.size() != n * nx || tau.size() != n * (size_t)(nv_ - 6))
+        throw std::runtime_error("X [n][nq + nv], tau [n][nv - 6] expected");
+      GroundDynamics g;
+      g.v_next.resize(n * nv_);
+      g.a.resize(n * nv_);
+      g.lambda.resize(n * 3 * (size_t)gn_);
+      g.gap.resize(n * (size_t)gn_);
+      g.contact.resize(n);
+      check(smpc_robot_sim_ground_dynamics(h_, (int)n, X.data(), tau.data(), dt, g.v_next.data(), g.a.data(), g.lambda.data(), g.gap.data(), g.contact.data()));
+      return g;
+    }
+    // forces [B][3 points] / contact words [B] of the last ground step (host copies; join the handle's stream)
+    std::vector<double> lastGroundForces()
+    {
+      std::vector<double> f((size_t)batch_ * 3 * gn_);
+      check(smpc_robot_sim_read_ground_last(h_, f.data(), nullptr));
+      return f;
+    }
+    std::vector<uint32_t> lastContacts()
+    {
+      std::vector<uint32_t> c((size_t)batch_);
+      check(smpc_robot_sim_read_ground_last(h_, nullptr, c.data()));
+      return c;
+    }
+    // the same as device pointers owned by the handle (they change when setGround is called again)
+    void groundForceDevicePointers(double ** lambda_device, uint32_t ** contact_device) { check(smpc_robot_sim_get_ground_last(h_, lambda_device, contact_device)); }
+
   private:
     static void check(int rc)
     {
@@ -106,6 +162,6 @@ namespace simple_mpc
         throw std::runtime_error("Kp, Kd: force_size Baumgarte gains each (or empty)");
     }
     smpc_robot_sim * h_ = nullptr;
-    int batch_ = 0, nq_ = 0, nv_ = 0, nf_ = 0, fs_ = 0;
+    int batch_ = 0, nq_ = 0, nv_ = 0, nf_ = 0, fs_ = 0, gp_ = 0, gn_ = 0;
   };
 } // namespace simple_mpc

@@ -581,6 +581,47 @@ int smpc_robot_sim_step_device(smpc_robot_sim * sim, double * X_device, const do
 int smpc_robot_sim_get_last(smpc_robot_sim * sim, double ** a_device, double ** lambda_device);
 int smpc_robot_sim_read_last(smpc_robot_sim * sim, double * a_out, double * lambda_out);
 
+/* ---- ground plane with unilateral frictional contact for the simulator above (simple-mpc_amd/csrc/smpc_sim_ground_rt.h) ----
+ * smpc_robot_sim_step_device applies the BILATERAL contacts its caller names; the entries below put the robot on a plane z = ground_z with
+ * unilateral contact and Coulomb friction DETECTED FROM THE STATE: no mask.  Every foot carries points_per_foot contact points (offsets
+ * in the foot frame, the same for every foot), numbered c = foot * points_per_foot + k; every point is always a row block [x y z] of a
+ * velocity-level complementarity problem that `sweeps` sweeps of projected Gauss-Seidel solve from lambda = 0 (no early exit), one kernel
+ * launch per step.  Independent of the handle's force_size.  A handle that never calls smpc_robot_sim_set_ground behaves as before.
+ *   smpc_ground_settings     ground_z; mu (friction coefficient); erp (share of a penetration removed per step); compliance (added to the
+ *                            diagonal of the Delassus matrix); sweeps; points_per_foot (1 .. 4); points[k][3].  An argument that is 0
+ *                            stands for its default: mu 0.7, erp 0.2, compliance 1e-8, sweeps 30, points_per_foot 1 with the point at
+ *                            the foot frame's origin (a frictionless or erp-free plane is a tiny positive value).
+ *   smpc_robot_sim_set_ground        stores the settings and (re)allocates the force and contact-word buffers; may be called again with
+ *                            other settings (another points_per_foot resizes the buffers); joins the handle's stream first.  Refused
+ *                            with SMPC_ERR_INVALID and a message that names the field, before anything is allocated and with the
+ *                            previous settings kept: a number that is not finite, mu < 0, erp outside [0, 1], compliance < 0,
+ *                            sweeps < 0, points_per_foot outside [0, 4], nfeet * points_per_foot > 8 (the message names the product).
+ *   smpc_robot_sim_get_ground_dims   dims[2] = points_per_foot, contact points per robot (nfeet points_per_foot); 0, 0 before set_ground
+ *   smpc_robot_sim_step_ground_device   one step of the batch: X_device [B][nq + nv] updated in place, tau_device [B][nv - 6].
+ *                            Asynchronous on the handle's stream.  dt <= 0, or a call before smpc_robot_sim_set_ground: SMPC_ERR_INVALID
+ *                            with a message.  Writes the accelerations a = M^-1 (S tau - h + J^T lambda) that smpc_robot_sim_get_last
+ *                            returns, the forces and the contact words.
+ *   smpc_robot_sim_ground_dynamics   the same solve on host buffers X [n][nq + nv], tau [n][nv - 6] (n need not be B); the state is not
+ *                            advanced.  v_next_out [n][nv], a_out [n][nv], lambda_out [n][3 points] (forces ON the robot in world axes,
+ *                            [point][x y z]), gap_out [n][points] (height of every point above the plane), contact_out [n] (bit c: the
+ *                            normal force of point c is positive); any output may be NULL.
+ *   smpc_robot_sim_get_ground_last   forces [B][3 points] and contact words [B] of the last ground step (device pointers owned by the
+ *                            handle; they change when smpc_robot_sim_set_ground is called again)
+ *   smpc_robot_sim_read_ground_last  the same copied to host buffers (either may be NULL); joins the handle's stream. */
+typedef struct smpc_ground_settings
+{
+  double ground_z, mu, erp, compliance;
+  int sweeps, points_per_foot;
+  double points[4][3];
+} smpc_ground_settings;
+int smpc_robot_sim_set_ground(smpc_robot_sim * sim, const smpc_ground_settings * settings);
+int smpc_robot_sim_get_ground_dims(smpc_robot_sim * sim, int * dims);
+int smpc_robot_sim_step_ground_device(smpc_robot_sim * sim, double * X_device, const double * tau_device, double dt);
+int smpc_robot_sim_ground_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, double * v_next_out, double * a_out,
+                                   double * lambda_out, double * gap_out, uint32_t * contact_out);
+int smpc_robot_sim_get_ground_last(smpc_robot_sim * sim, double ** lambda_device, uint32_t ** contact_device);
+int smpc_robot_sim_read_ground_last(smpc_robot_sim * sim, double * lambda_out, uint32_t * contact_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 #include "smpc_id.h"
 #include "smpc_id_rt.h"
 #include "smpc_sim_rt.h"
+#include "smpc_sim_ground_rt.h"
 #include "smpc_robot_check.h"
 #include <atomic>
 #include <cstring>
@@ -32,6 +33,7 @@ typedef FullDims<23, 2, 6, 0, 0, 1> KinoTalos;  // KINODYNAMICS OCP of the Talos
 struct smpc_robot_sim // stand-alone simulator handle: a robot table and nothing else (smpc_sim_rt.h)
 {
   std::unique_ptr<RobotSimRt> e;
+  std::unique_ptr<RobotSimGround> g; // the ground plane, once smpc_robot_sim_set_ground has been called (destroyed before the engine it refers to)
 };
 
 struct smpc_handle
@@ -1274,5 +1276,72 @@ extern "C"
     if (!sim)
       return fail(SMPC_ERR_INVALID, "null argument");
     return guarded([&] { sim->e->read_last(a_out, lambda_out); });
+  }
+
+  // ---- ground plane with unilateral frictional contact (smpc_sim_ground_rt.h) ----
+  int smpc_robot_sim_set_ground(smpc_robot_sim * sim, const smpc_ground_settings * settings)
+  {
+    if (!sim || !settings)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    // admission before anything else: nothing is allocated, and the previous settings stay, for settings the kernel is not built for
+    const std::string why = sim_ground_admission_error(sim->e->sz.nfeet, settings);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      sim->e->wait(); // (a step in flight still writes the buffers that are replaced below)
+      std::unique_ptr<RobotSimGround> g(new RobotSimGround(*sim->e, settings));
+      sim->g = std::move(g);
+    });
+  }
+  int smpc_robot_sim_get_ground_dims(smpc_robot_sim * sim, int * dims)
+  {
+    if (!sim || !dims)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    dims[0] = sim->g ? sim->g->gz.P : 0;
+    dims[1] = sim->g ? sim->g->gz.npts : 0;
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_step_ground_device(smpc_robot_sim * sim, double * X_device, const double * tau_device, double dt)
+  {
+    if (!sim || !X_device || !tau_device)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_step_ground_device: no ground yet, call smpc_robot_sim_set_ground first");
+    if (!(dt > 0.0) || !std::isfinite(dt))
+      return fail(SMPC_ERR_INVALID, "dt must be positive");
+    return guarded([&] { sim->g->step_device(X_device, tau_device, dt); });
+  }
+  int smpc_robot_sim_ground_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, double * v_next_out, double * a_out,
+                                     double * lambda_out, double * gap_out, uint32_t * contact_out)
+  {
+    if (!sim || !X || !tau)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_ground_dynamics: no ground yet, call smpc_robot_sim_set_ground first");
+    if (n < 1)
+      return fail(SMPC_ERR_INVALID, "n must be positive");
+    if (!(dt > 0.0) || !std::isfinite(dt))
+      return fail(SMPC_ERR_INVALID, "dt must be positive");
+    return guarded([&] { sim->g->dynamics(n, X, tau, dt, v_next_out, a_out, lambda_out, gap_out, contact_out); });
+  }
+  int smpc_robot_sim_get_ground_last(smpc_robot_sim * sim, double ** lambda_device, uint32_t ** contact_device)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_get_ground_last: no ground yet, call smpc_robot_sim_set_ground first");
+    if (lambda_device)
+      *lambda_device = sim->g->lam;
+    if (contact_device)
+      *contact_device = sim->g->contact;
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_read_ground_last(smpc_robot_sim * sim, double * lambda_out, uint32_t * contact_out)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_read_ground_last: no ground yet, call smpc_robot_sim_set_ground first");
+    return guarded([&] { sim->g->read_last(lambda_out, contact_out); });
   }
 }

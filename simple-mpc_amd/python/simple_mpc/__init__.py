@@ -1570,6 +1570,87 @@ class BatchedRobotSim:
         self._lib.check(self._lib.L.smpc_robot_sim_read_last(self._h, None, lam.ctypes.data))
         return lam
 
+    # ---- ground plane with unilateral frictional contact (simple-mpc_amd/csrc/smpc_sim_ground_rt.h) ----
+    _GROUND_KEYS = ("ground_z", "mu", "erp", "compliance", "sweeps", "points_per_foot", "points")
+
+    def setGround(self, **settings):
+        """Put the robots on the plane z = ground_z with unilateral contact and Coulomb friction detected from the state (no contact mask).
+        Keywords: ground_z, mu, erp, compliance, sweeps, points_per_foot (1 .. 4) and points [points_per_foot][3] (offsets in the foot
+        frame, the same for every foot); a value of 0, or a keyword left out, stands for the default (mu 0.7, erp 0.2, compliance 1e-8,
+        sweeps 30, one point at the foot frame's origin).  May be called again; nfeet * points_per_foot <= 8."""
+        for k in settings:
+            if k not in self._GROUND_KEYS:
+                raise RuntimeError("setGround: unknown setting %r (one of %s)" % (k, ", ".join(self._GROUND_KEYS)))
+        g = _capi.GroundSettingsC()
+        for k in ("ground_z", "mu", "erp", "compliance"):
+            setattr(g, k, float(settings.get(k, 0.0)))
+        g.sweeps = int(settings.get("sweeps", 0))
+        pts = settings.get("points")
+        if pts is not None:
+            pts = np.array(pts, dtype=np.float64)
+            if pts.ndim != 2 or pts.shape[1] != 3 or not 1 <= pts.shape[0] <= 4:
+                raise RuntimeError("setGround: points [points_per_foot][3] with 1 .. 4 points expected")
+        g.points_per_foot = int(settings.get("points_per_foot", 0 if pts is None else pts.shape[0]))
+        if g.points_per_foot > 0:
+            if pts is None and g.points_per_foot == 1:
+                pts = np.zeros((1, 3))
+            if pts is None or pts.shape[0] != g.points_per_foot:
+                raise RuntimeError("setGround: points_per_foot = %d needs that many points [k][3]" % g.points_per_foot)
+            for k in range(pts.shape[0]):
+                for i in range(3):
+                    g.points[k][i] = pts[k, i]
+        self._lib.check(self._lib.L.smpc_robot_sim_set_ground(self._h, C.byref(g)))
+        d = (C.c_int * 2)()
+        self._lib.check(self._lib.L.smpc_robot_sim_get_ground_dims(self._h, d))
+        self.ground_points_per_foot, self.ground_points = int(d[0]), int(d[1])
+
+    def _ground_npts(self):
+        d = (C.c_int * 2)()
+        self._lib.check(self._lib.L.smpc_robot_sim_get_ground_dims(self._h, d))
+        return int(d[1])
+
+    def stepGroundDevice(self, x_ptr, tau_ptr, dt):
+        """One step on the ground of setGround with states [B][nq + nv] and torques [B][nv - 6] resident on the device: the contact forces
+        of every point from the state, v <- v + a dt, q <- integrate(q, v dt); the states are updated in place.  Asynchronous on the
+        handle's stream (wait() joins).  lastAccelerations(), lastGroundForces() and lastContacts() read its results."""
+        if not float(dt) > 0.0:
+            raise RuntimeError("dt must be positive")
+        self._lib.check(self._lib.L.smpc_robot_sim_step_ground_device(self._h, C.c_void_p(int(x_ptr)), C.c_void_p(int(tau_ptr)), float(dt)))
+
+    def groundDynamics(self, X, tau, dt):
+        """The solve of one ground step for states X[n, nq + nv] and torques tau[n, nv - 6] on the host (n need not be the batch; nothing is
+        advanced): dict(v_next[n, nv], a[n, nv], lam[n, 3 points] (forces on the robot in world axes, [point][x y z]), gap[n, points]
+        (height of every point above the plane), contact[n] (bit c: point c carries a positive normal force))."""
+        X = np.ascontiguousarray(np.array(X, dtype=np.float64))
+        tau = np.ascontiguousarray(np.array(tau, dtype=np.float64))
+        n = X.shape[0] if X.ndim == 2 else 0
+        if n < 1 or X.shape[1] != self.nq + self.nv or tau.shape != (n, self.nv - 6):
+            raise RuntimeError("X [n, nq + nv], tau [n, nv - 6] expected")
+        npts = self._ground_npts()
+        v, a, lam, gap, con = np.zeros((n, self.nv)), np.zeros((n, self.nv)), np.zeros((n, 3 * npts)), np.zeros((n, npts)), np.zeros(n, np.uint32)
+        self._lib.check(self._lib.L.smpc_robot_sim_ground_dynamics(self._h, n, X, tau, float(dt), v.ctypes.data, a.ctypes.data, lam.ctypes.data,
+                                                                   gap.ctypes.data, con.ctypes.data))
+        return dict(v_next=v, a=a, lam=lam, gap=gap, contact=con)
+
+    def lastGroundForces(self):
+        """Contact forces [B, 3 points] of the last ground step (host copy; joins the handle's stream)."""
+        lam = np.zeros((self.B, 3 * self._ground_npts()))
+        self._lib.check(self._lib.L.smpc_robot_sim_read_ground_last(self._h, lam.ctypes.data, None))
+        return lam
+
+    def lastContacts(self):
+        """Contact words [B] (uint32, bit per contact point) of the last ground step (host copy; joins the handle's stream)."""
+        con = np.zeros(self.B, np.uint32)
+        self._lib.check(self._lib.L.smpc_robot_sim_read_ground_last(self._h, None, con.ctypes.data))
+        return con
+
+    def groundForceDevicePointers(self):
+        """(contact forces [B][3 points], contact words [B]) of the last ground step as device pointers owned by the handle; they change
+        when setGround is called again."""
+        lam, con = C.c_void_p(), C.c_void_p()
+        self._lib.check(self._lib.L.smpc_robot_sim_get_ground_last(self._h, C.byref(lam), C.byref(con)))
+        return int(lam.value), int(con.value)
+
 
 class FrictionCompensation:
     """reference include/simple-mpc/friction-compensation.hpp: torque += viscuous * v + dry * sign(v).  The reference reads

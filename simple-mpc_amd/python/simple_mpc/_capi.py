@@ -146,6 +146,18 @@ class RobotModelC(C.Structure):
     ]
 
 
+class GroundSettingsC(C.Structure):  # smpc_ground_settings
+    _fields_ = [
+        ("ground_z", C.c_double),
+        ("mu", C.c_double),
+        ("erp", C.c_double),
+        ("compliance", C.c_double),
+        ("sweeps", C.c_int),
+        ("points_per_foot", C.c_int),
+        ("points", (C.c_double * 3) * 4),
+    ]
+
+
 # every symbol declared in include/smpc.h
 SYMBOLS = [
     "smpc_builtin_robot", "smpc_last_error", "smpc_device_count", "smpc_create", "smpc_create_centroidal", "smpc_create_fulldynamics", "smpc_get_contact_forces", "smpc_destroy", "smpc_get_dims",
@@ -159,6 +171,7 @@ SYMBOLS = [
     "smpc_interpolate", "smpc_interpolate_knots", "smpc_friction_compensation", "smpc_update_internal_data", "smpc_debug_frontend_rt", "smpc_full_forward_dynamics", "smpc_centroidal_dynamics", "smpc_riccati_feedback",
     "smpc_id_create", "smpc_id_create_any", "smpc_id_destroy", "smpc_id_set_target", "smpc_id_set_targets", "smpc_id_set_target_centroidal", "smpc_id_set_targets_centroidal", "smpc_id_solve", "smpc_id_solve_device", "smpc_id_wait", "smpc_id_get_resid", "smpc_id_reset", "smpc_id_get_tau_device", "smpc_id_get_x_device", "smpc_id_set_targets_from_mpc", "smpc_id_share_stream", "smpc_sim_step_device", "smpc_id_debug_get", "smpc_id_get_dims", "smpc_debug_id_force_rt",
     "smpc_robot_sim_create", "smpc_robot_sim_destroy", "smpc_robot_sim_get_dims", "smpc_robot_sim_wait", "smpc_robot_sim_get_stream", "smpc_robot_sim_share_stream", "smpc_robot_sim_forward_dynamics", "smpc_robot_sim_step_device", "smpc_robot_sim_get_last", "smpc_robot_sim_read_last",
+    "smpc_robot_sim_set_ground", "smpc_robot_sim_get_ground_dims", "smpc_robot_sim_step_ground_device", "smpc_robot_sim_ground_dynamics", "smpc_robot_sim_get_ground_last", "smpc_robot_sim_read_ground_last",
 ]
 
 
@@ -295,6 +308,12 @@ class SmpcLib:
         L.smpc_robot_sim_step_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_double]
         L.smpc_robot_sim_get_last.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.smpc_robot_sim_read_last.argtypes = [vp, vp, vp]
+        L.smpc_robot_sim_set_ground.argtypes = [vp, C.POINTER(GroundSettingsC)]
+        L.smpc_robot_sim_get_ground_dims.argtypes = [vp, C.POINTER(C.c_int)]
+        L.smpc_robot_sim_step_ground_device.argtypes = [vp, vp, vp, C.c_double]
+        L.smpc_robot_sim_ground_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, vp, vp, vp, vp, vp]
+        L.smpc_robot_sim_get_ground_last.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.smpc_robot_sim_read_ground_last.argtypes = [vp, vp, vp]
 
     def check(self, code):
         if code < 0:

@@ -8,7 +8,17 @@ kernel on a run-time joint tree (sim_rt_body) side by side.
 quad_arm, the 32-joint point-foot table of tests/test_id_any_robot.py and tree32 with two 6-D contacts, one after the other; every foot in
 contact, Baumgarte gains (0, 50), small random torques; per robot WARM steps, then READINGS x LAUNCHES steps -- the states move between
 launches because every step integrates them.  `summary`: the dispatches of the trace whose grid is the full batch, per kernel in launch
-order, cut into the robots' runs; per reading the mean of its LAUNCHES dispatches, then the minimum of the readings and their spread."""
+order, cut into the robots' runs; per reading the mean of its LAUNCHES dispatches, then the minimum of the readings and their spread.
+
+The ground plane, same method:
+
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -o ground -- python3 tools/sim_rt_profile.py run-ground [batch]
+    python3 tools/sim_rt_profile.py summary-ground <kernel_trace.csv> [batch]
+
+`run-ground`: per robot of GROUND_RUNS BatchedRobotSim.stepDevice (sim_rt_body, every foot in contact: the yardstick of the same run), then
+stepGroundDevice with the plane at the reference foot height on both instantiations (a points-per-foot count that gives at most 12 rows,
+one that gives more) at each of GROUND_SWEEPS sweeps.  `summary-ground`: one row per run, and the cost of a sweep as the slope between
+the smallest and the largest sweep count."""
 import collections
 import csv
 import os
@@ -18,6 +28,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WARM, READINGS, LAUNCHES = 5, 3, 20
 RUNS = [("go2_like", 3, False), ("go2_like", 3, True), ("quad_arm", 3, True), ("tree32p", 3, True), ("tree32", 6, True)]  # (robot, contact size, run-time kernel)
+GROUND_SWEEPS = (10, 30, 60)
+# (robot, contact size of the bilateral yardstick, points per foot on sim_ground_rt_body<12>, on <24>)
+GROUND_RUNS = [("go2_like", 3, 1, 2), ("quad_arm", 3, 1, 2), ("tree32p", 3, 1, 2), ("biped_legs", 6, 1, 4)]
+GROUND_POINTS = {1: [(0.0, 0.0, 0.0)], 2: [(0.02, 0.0, 0.0), (-0.02, 0.0, 0.0)], 4: [(0.1, 0.05, 0.0), (0.1, -0.05, 0.0), (-0.1, 0.05, 0.0), (-0.1, -0.05, 0.0)]}
 
 
 def run(B):
@@ -48,6 +62,69 @@ def run(B):
         sim.wait()
         Xh = Xd.cpu().numpy()
         print(name, "fs", fs, "run-time" if rt else "templated", "finite:", bool(np.isfinite(Xh).all()), "largest state change %.3f" % np.abs(Xh - X).max(), flush=True)
+
+
+def run_ground(B):
+    sys.path[:0] = [os.path.join(ROOT, "simple-mpc_amd", "python"), os.path.join(ROOT, "tests")]
+    import numpy as np
+    import torch
+    import robot_tables as RT
+    import simple_mpc
+    import test_id_any_robot as T
+
+    for name, fs, p12, p24 in GROUND_RUNS:
+        tab = T.table(name)
+        rb = RT.oracle_robot(tab)
+        sim = simple_mpc.BatchedRobotSim(RT.model_handler(tab), force_size=fs, batch=B)
+        gz = float(rb.centroidal(rb.x_ref)["feet"][:, 2].min())
+        X = RT.near_reference_states(rb, min(B, 64), seed=5, scale=0.3)
+        X = np.tile(X, (-(-B // X.shape[0]), 1))[:B]
+        td = torch.from_numpy(np.random.default_rng(6).normal(0.0, 1.0, (B, rb.nv - 6))).cuda()
+        runs = [("sim_rt_body", None, None)] + [("ground", P, sw) for P in (p12, p24) for sw in GROUND_SWEEPS]
+        for kind, P, sw in runs:
+            if kind == "ground":
+                sim.setGround(ground_z=gz, points=GROUND_POINTS[P], sweeps=sw)
+                step = lambda x, t: sim.stepGroundDevice(x, t, 1e-3)
+            else:
+                step = lambda x, t: sim.stepDevice(x, t, [True] * tab.nfeet, 1e-3, Kp=[0.0] * fs, Kd=[50.0] * fs)
+            Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
+            torch.cuda.synchronize()
+            for _ in range(WARM + READINGS * LAUNCHES):
+                step(Xd.data_ptr(), td.data_ptr())
+            sim.wait()
+            Xh = Xd.cpu().numpy()
+            note = "" if kind != "ground" else " robots with a contact %d of %d" % (int((sim.lastContacts() != 0).sum()), B)
+            print(name, kind, "P", P, "sweeps", sw, "finite:", bool(np.isfinite(Xh).all()), "largest state change %.3f" % np.abs(Xh - X).max() + note, flush=True)
+
+
+def summary_ground(trace, B):
+    d = []  # (kernel, rows of the instantiation, duration) in launch order
+    for r in sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"])):
+        grid = int(r["Grid_Size"]) if "Grid_Size" in r else int(r["Grid_Size_X"])
+        m = re.search(r"(sim_rt_body|sim_ground_rt_body(?:<|ILi)(\d+))", r["Kernel_Name"])
+        if m and grid == B * 64:
+            d.append(("sim_rt_body" if m.group(2) is None else "sim_ground_rt_body<%s>" % m.group(2), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3))
+    per = WARM + READINGS * LAUNCHES
+    assert len(d) == per * len(GROUND_RUNS) * (1 + 2 * len(GROUND_SWEEPS)), len(d)
+    print("| robot | kernel | points | sweeps | step µs | spread of the readings | per sweep µs |")
+    print("|---|---|---|---|---|---|---|")
+    k = 0
+    for name, fs, p12, p24 in GROUND_RUNS:
+        for P in (None, p12, p24):
+            times = []
+            for sw in ((None,) if P is None else GROUND_SWEEPS):
+                blk = d[k * per: (k + 1) * per]
+                k += 1
+                assert len(set(n for n, _ in blk)) == 1, set(n for n, _ in blk)
+                t = [v for _, v in blk[WARM:]]
+                means = [sum(t[i * LAUNCHES: (i + 1) * LAUNCHES]) / LAUNCHES for i in range(READINGS)]
+                times.append(min(means))
+                slope = "" if sw != GROUND_SWEEPS[-1] else "%.2f" % ((times[-1] - times[0]) / (GROUND_SWEEPS[-1] - GROUND_SWEEPS[0]))
+                print("| %s | `%s` | %s | %s | %.1f | %.1f %% | %s |" % (name, blk[0][0], "%d-D bilateral" % fs if P is None else str(P * T_NFEET[name]), sw or "", min(means),
+                                                                       100 * (max(means) / min(means) - 1.0), slope))
+
+
+T_NFEET = {"go2_like": 4, "quad_arm": 4, "tree32p": 4, "biped_legs": 2}
 
 
 def summary(trace, B):
@@ -85,5 +162,9 @@ def summary(trace, B):
 if __name__ == "__main__":
     if sys.argv[1] == "run":
         run(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+    elif sys.argv[1] == "run-ground":
+        run_ground(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+    elif sys.argv[1] == "summary-ground":
+        summary_ground(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 4096)
     else:
         summary(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 4096)
