@@ -317,6 +317,7 @@ namespace smpc
       buf.vbase = vbase_dev = dalloc((size_t)B * 6);
       buf.vref = dalloc(BR * 6);
       buf.lq = dalloc(BH * D::LQ_STRIDE);
+      buf.lqc = dalloc(D::N_CT); // (written once, by lq_init_body below)
       buf.gains = dalloc(BH * (size_t)std::max((int)D::G_STRIDE, (int)GainsK<D>::STRIDE));
       if (lane_eval && m.lane_slots > 0 && !ks.terminal_constraint && !ks.force_cone && !ks.land_cstr)
       {
@@ -753,8 +754,11 @@ namespace smpc
         throw InvalidCall("Stage index exceeds stage vector size");
       // the device keeps [Q S; S^T R] as accumulator-layout tiles (Dims::O_T); returned in the documented row-major order
       // A | B | Q | S | R | C | q | r | f | d | lx | lu | lpd | vpd
-      std::vector<double> raw(D::LQ_STRIDE);
+      // (the last tile column of the grid is the handle's image, its diagonal and the selectors of the box rows of C two runs of the knot:
+      // Dims::S_at / R_at / C_at put them back where the row-major form has them)
+      std::vector<double> raw(D::LQ_STRIDE), img(D::N_CT);
       get_linear(buf.lq + ((size_t)inst * H + t) * D::LQ_STRIDE, D::LQ_STRIDE, raw.data());
+      get_linear(buf.lqc, D::N_CT, img.data());
       constexpr int n = D::NDX, m = D::NU;
       double * o = out;
       std::copy(raw.begin() + D::O_A, raw.begin() + D::O_T, o); // A | B
@@ -764,11 +768,14 @@ namespace smpc
           *o++ = raw[D::q_off(i, j)];
       for (int i = 0; i < n; i++)
         for (int j = 0; j < m; j++)
-          *o++ = raw[D::s_off(i, j)];
+          *o++ = D::S_at(raw.data(), img.data(), i, j);
       for (int i = 0; i < m; i++)
         for (int j = 0; j < m; j++)
-          *o++ = raw[D::r_off(i, j)];
-      std::copy(raw.begin() + D::O_C, raw.begin() + D::O_vpd + D::NC, o);
+          *o++ = D::R_at(raw.data(), img.data(), i, j);
+      for (int r = 0; r < D::NC; r++)
+        for (int j = 0; j < n; j++)
+          *o++ = D::C_at(raw.data(), r, j);
+      std::copy(raw.begin() + D::O_q, raw.begin() + D::O_vpd + D::NC, o);
     }
   };
 } // namespace smpc

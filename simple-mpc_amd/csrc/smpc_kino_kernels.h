@@ -373,8 +373,7 @@ namespace smpc
         double q = g + acc + cn - (t > 0 ? lam_prev_v : 0.0);
         if (t == 0)
           q = 0.0; // x_0 is pinned (force_initial_condition_, reference src/mpc.cpp:53)
-        lq[D::O_q + k] = q;
-        lq[D::t_off(k, D::NXU)] = q; // (column NXU of the tile grid: the vector column of the structured sweep, loaded with its tiles)
+        lq[D::O_q + k] = q; // ([q | r] is also the vector column NXU of the tile grid: the structured sweep patches it into its tiles)
         lq[D::O_lx + k] = g;
         lq[D::O_f + k] = mu * (sc.lamp[k] - sc.lam_next[k]);
         lq[D::O_lpd + k] = 2.0 * sc.lamp[k] - sc.lam_next[k];
@@ -405,7 +404,6 @@ namespace smpc
             r += j0[k % 3] * cs[6 * NF + 2 * f] + j1[k % 3] * cs[6 * NF + 2 * f + 1];
         }
         lq[D::O_r + k] = r;
-        lq[D::t_off(NDX + k, D::NXU)] = r;
         lq[D::O_lu + k] = g;
         sc.ru[k] = fabs(r);
       }
@@ -624,20 +622,21 @@ namespace smpc
             }
           }
         // columns / rows of the joint accelerations (u indices >= UC): no Jacobian entries.  Their S columns (zero)
-        // and the off-diagonal R entries (weights) are constant and written once by lq_init_body; only the diagonal
-        // carries the current primal regularisation
-        constexpr int UC = 16 * 3 - NDX; // u columns covered by the tiles
+        // and the off-diagonal R entries (weights) are constant: the handle's image of the last tile column (Dims::CT_J,
+        // lq_init_body); only the diagonal carries the current primal regularisation -- one contiguous run of the knot
+        constexpr int UC = D::UC; // u columns covered by the tiles
+        static_assert(D::CT_J == 3, "the six tiles above are the grid without its last tile column");
         if (lane >= UC && lane < NU)
-          lq[D::r_off(lane, lane)] = (md.w_diag ? md.wud[lane] : mg.w_u[lane * NU + lane]) + preg;
+          lq[D::O_rdiag + lane - UC] = (md.w_diag ? md.wud[lane] : mg.w_u[lane * NU + lane]) + preg;
       }
       SMPC_LANES_END_WAVE
     }
     SMPC_LANES(NT)
     {
-      // joint-box rows of C: unit selectors when active (the zeros of these rows are written once by lq_init_body, the
-      // contact rows with the constraint Jacobian columns), d, vpd
+      // joint-box rows of C: unit selectors when active, kept as one run of 0 / 1 (Dims::O_box; the rows themselves stay the
+      // zeros lq_init_body wrote.  The contact rows were written with the constraint Jacobian columns), d, vpd
       if (lane < NA)
-        lq[D::O_C + lane * NDX + 6 + lane] = sc.act[lane] ? 1.0 : 0.0;
+        lq[D::O_box + lane] = sc.act[lane] ? 1.0 : 0.0;
       if (lane < NC)
       {
         lq[D::O_d + lane] = mu * (sc.vplus[lane] - sc.nu[lane]);
@@ -1037,34 +1036,42 @@ namespace smpc
       }
     }
     SMPC_LANES_END_WAVE
-    // blocks without Jacobian entries: S columns and off-diagonal R entries of the joint accelerations, the zeros of the
-    // joint-box rows of C
+    // the tiles the derivative pass writes (the padding entries beyond the problem are loaded by the sweep and must be finite), the two runs it
+    // keeps in the block of the last tile (Dims::O_rdiag, O_box), the joint-box rows of C (zeros: their selectors are at O_box)
     SMPC_LANES(NT)
     {
-      // (first the whole tile block: the padding entries beyond the problem are loaded by the sweep and must be finite)
       for (int idx = lane; idx < D::N_T; idx += NT)
-        lq[D::O_T + idx] = 0.0;
-    }
-    SMPC_LANES_END_WAVE
-    SMPC_LANES(NT)
-    {
-      constexpr int UC = 16 * 3 - NDX, NA = D::NA;
-      const DevModel<D> & mg = *ka.b.model;
-      for (int idx = lane; idx < NU * NU; idx += NT)
       {
-        const int i = idx / NU, j = idx % NU;
-        if ((i >= UC || j >= UC) && i != j)
-        { // off-diagonal weights of the joint accelerations; inside a diagonal tile both triangles are kept
-          if (i < j)
-            lq[D::r_off(i, j)] = mg.w_u[idx];
-          else if ((NDX + i) / 16 == (NDX + j) / 16)
-            lq[D::O_T + ((((NDX + j) / 16) * D::NTT - ((NDX + j) / 16) * ((NDX + j) / 16 - 1) / 2) * 4 + ((NDX + i) % 16) / 4) * 64 + (((NDX + i) % 16) % 4) * 16 + (NDX + j) % 16] = mg.w_u[idx];
-        }
+        const int tile = idx / 256;
+        bool constant = false; // tile (I, CT_J): kept once per handle
+        for (int I = 0; I < D::NTT; I++)
+          constant = constant || tile == I * D::NTT - I * (I - 1) / 2 + (D::CT_J - I);
+        if (!constant)
+          lq[D::O_T + idx] = 0.0;
       }
-      for (int idx = lane; idx < NA * NDX; idx += NT)
+      if (lane < 32)
+        lq[D::O_rdiag + lane] = 0.0;
+      for (int idx = lane; idx < D::NA * NDX; idx += NT)
         lq[D::O_C + idx] = 0.0;
     }
     SMPC_LANES_END_WAVE
+    // The constant tile column of [Q S; S^T R] (Dims::CT_J): zeros (S columns of the joint accelerations, padding) and the weights w_u, the diagonal
+    // without the primal regularisation; inside the diagonal tile both triangles.  ONE image per handle, written here by block 0 alone, once.
+    if (block == 0)
+    {
+      SMPC_LANES(NT)
+      {
+        const DevModel<D> & mg = *ka.b.model;
+        double * lqc = ka.b.lqc;
+        for (int idx = lane; idx < D::N_CT; idx += NT)
+        {
+          // element v of lane l of tile (I, CT_J): entry (16 I + (l >> 4) + 4 v, 16 CT_J + (l & 15))
+          const int r = 16 * (idx / 256) + ((idx % 64) >> 4) + 4 * ((idx % 256) / 64), c = 16 * D::CT_J + (idx & 15);
+          lqc[idx] = (r >= NDX && r < D::NXU && c < D::NXU) ? mg.w_u[(r - NDX) * NU + c - NDX] : 0.0;
+        }
+      }
+      SMPC_LANES_END_WAVE
+    }
   }
 
   // =============================================================================================

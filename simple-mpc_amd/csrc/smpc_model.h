@@ -43,6 +43,36 @@ namespace smpc
     SMPC_HD static constexpr int q_off(int i, int j) { return i <= j ? t_off(i, j) : t_off(j, i); }      // Q(i, j)
     SMPC_HD static constexpr int s_off(int i, int j) { return t_off(i, NDX + j); }                        // S(i, j)
     SMPC_HD static constexpr int r_off(int i, int j) { return i <= j ? t_off(NDX + i, NDX + j) : t_off(NDX + j, NDX + i); } // R(i, j)
+    // The LAST tile column (CT_J; u columns >= UC, all of them joint accelerations, and the padding) has no Jacobian entries: its S columns are
+    // zero and its R entries are the weights w_u.  Its NTT tiles are NOT kept per knot: one image per handle (Buffers::lqc, N_CT doubles: tile
+    // (I, CT_J) at I * 256 in the same accumulator layout, diagonal = the plain weight WITHOUT the primal regularisation) holds them, and the
+    // per-knot slots of these tiles stay unused but for two contiguous runs in the block of the last tile that the derivative pass writes every
+    // iteration:   O_rdiag: R(UC + k, UC + k) = w + preg of the derivation, k < NU - UC     O_box: 0 / 1 selectors of the NA joint-box rows of C.
+    // The vector column NXU of the grid (the structured sweep wants q | r there) is [q | r] at O_q, and the box rows of C at O_C are zeros
+    // but for the selector (row k, column 6 + k).  Readers of single entries go through H_at / R_at / S_at / C_at below.
+    // SINGLE WRITER of the image: block 0 of lq_init_body, launched once by the handle's constructor before any sweep; nothing writes it
+    // afterwards (every wave of every later launch reads it concurrently).
+    static constexpr int CT_J = NTT - 1;
+    static constexpr int UC = 16 * CT_J - NDX;
+    static constexpr int N_CT = NTT * 256;
+    static constexpr int O_rdiag = O_T + N_T - 256;
+    static constexpr int O_box = O_rdiag + 16;
+    static_assert(UC >= 3 * NF && UC < NU && NXU % 16 != 0 && NXU > 16 * CT_J && NU - UC <= 16 && NA <= 240, "geometry of the constant tile column");
+    SMPC_HD static constexpr int ct_off(int r, int c) { return (((r / 16) * 4 + (r % 16) / 4) * 64) + ((r % 16) % 4) * 16 + c % 16; } // c / 16 == CT_J
+    // entry (r, c) of the grid [Q S q; S^T R r], r / 16 <= c / 16, r < NXU, c <= NXU, of a knot `lq` and the handle's image `lqc`
+    SMPC_HD static double H_at(const double * lq, const double * lqc, int r, int c)
+    {
+      if (c / 16 != CT_J)
+        return lq[t_off(r, c)];
+      if (c == NXU)
+        return lq[O_q + r]; // (O_r == O_q + NDX)
+      if (r == c)
+        return lq[O_rdiag + r - NDX - UC];
+      return lqc[ct_off(r, c)];
+    }
+    SMPC_HD static double S_at(const double * lq, const double * lqc, int i, int j) { return H_at(lq, lqc, i, NDX + j); }
+    SMPC_HD static double R_at(const double * lq, const double * lqc, int i, int j) { return i <= j ? H_at(lq, lqc, NDX + i, NDX + j) : H_at(lq, lqc, NDX + j, NDX + i); }
+    SMPC_HD static double C_at(const double * lq, int r, int j) { return r >= NA ? lq[O_C + r * NDX + j] : (j == 6 + r ? lq[O_box + r] : 0.0); }
     static constexpr int O_C = O_T + N_T;
     static constexpr int O_q = O_C + NC * NDX;
     static constexpr int O_r = O_q + NDX;
@@ -144,6 +174,7 @@ namespace smpc
     double *vbase = nullptr, *vref = nullptr;
     // LQ + gains
     double *lq = nullptr, *gains = nullptr;
+    double * lqc = nullptr; // [Dims::N_CT] the constant tile column of [Q S; S^T R], one image per handle shared by every instance and part (Dims::CT_J)
     // lane-per-problem stage evaluation (smpc_kino_lane.h): one block per (instance, stage), [B][H+1][EvLayout::STRIDE]; the
     // working set of the evaluating lane and the hand-over to the derivative kernel.  nullptr: the handle does not use it.
     double * ev = nullptr;

@@ -556,18 +556,33 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
       prof_tick(prof, 4, tprev);
       // ---- (3b) register prefetch of [Q S; S^T R] in accumulator-tile layout (element (row, col) of tile (I, J):
       //           row = 16 I + (lane >> 4) + 4 v, col = 16 J + (lane & 15)); the HBM/L2 latency overlaps with the
-      //           P~ E passes and the TG product below.  Column NXU of the grid is the vector column of the second sweep: the derivative pass
-      //           stores q / r there as well (smpc_kino_kernels.h) ----
+      //           P~ E passes and the TG product below.  The last tile column (Dims::CT_J) is not in the knot: its registers come from the handle's
+      //           image (one base for every wave: cache resident), but for the lanes of column NXU -- the vector column of the second sweep: [q | r]
+      //           of the knot -- and of the diagonal of R (Dims::O_rdiag).  Address selects: still one load per register, nothing to wait for ----
       SMPC_LANES(NT)
       {
+        static_assert(D::CT_J == 3 && NXU % 16 == 12 && D::O_r == D::O_q + NDX, "tile column 3 = image | [q | r] in column 60");
+        const int lr = lane >> 4, lc = lane & 15;
+        const bool vcol = lc == NXU % 16;
+        // register n = 4 I + v of the column: image at 64 n + lane, vector column at 4 n + lr -- a base and a stride per lane
+        const double * pc = vcol ? lq + D::O_q + lr : b.lqc + lane;
+        const int ps = vcol ? 4 : 64;
 #pragma unroll
         for (int tt = 0; tt < 10; tt++)
 #pragma unroll
           for (int v = 0; v < 4; v++)
           {
-            // the knot keeps the tiles in this layout (Dims::O_T): one 512-byte run per accumulator register, no address arithmetic
+            // the knot keeps the other tiles in this layout (Dims::O_T): one 512-byte run per accumulator register, no address arithmetic
             // (padding entries beyond the problem are zeros written once by lq_init_body; they only ever feed themselves)
-            SMPC_ACCV(hacc, tt, v) = lq[D::O_T + (tt * 4 + v) * 64 + lane];
+            const int I = T4I[tt], J = T4J[tt];
+            if (J != 3)
+              SMPC_ACCV(hacc, tt, v) = lq[D::O_T + (tt * 4 + v) * 64 + lane];
+            else if (I != 3)
+              SMPC_ACCV(hacc, tt, v) = pc[(4 * I + v) * ps];
+            else if (v != 3)
+              SMPC_ACCV(hacc, tt, v) = *(lc == lr + 4 * v ? lq + D::O_rdiag + lc : pc + (12 + v) * ps); // (diagonal of R: w + preg of the derivation)
+            else
+              SMPC_ACCV(hacc, tt, v) = b.lqc[(12 + v) * 64 + lane]; // (rows NXU ..: padding)
           }
       }
       SMPC_LANES_END_WAVE
@@ -586,9 +601,8 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
         // do not survive the products' accumulator tiles (the compiler spilled them right after the load, i.e. waited for
         // every one of them), so the lines are only TOUCHED here -- one 4-byte load per 64-byte line into an LDS sink, no
         // register and no wait -- which brings them into L2; the real loads in (5) then return in one L2 round trip.
-        static_assert(NG * NDX <= 54 * 8 && NA + NG <= 24 && NA <= NT, "line touches: 54 lines of C, 3 of d, one per box row");
-        SMPC_TOUCH(lq + (lane < 54 ? D::O_C + NA * NDX + lane * 8 : D::O_d + (lane < 57 ? (lane - 54) * 8 : 0)), s.sink);
-        SMPC_TOUCH(lq + D::O_C + (lane < NA ? lane * NDX + 6 + lane : 0), s.sink);
+        static_assert(NG * NDX <= 54 * 8 && NA + NG <= 24 && NA <= 16, "line touches: 54 lines of C, 3 of d, 2 of the box selectors");
+        SMPC_TOUCH(lq + (lane < 54 ? D::O_C + NA * NDX + lane * 8 : (lane < 57 ? D::O_d + (lane - 54) * 8 : D::O_box + (lane & 1) * 8)), s.sink);
       }
       SMPC_LANES_END_WAVE
       prof_tick(prof, 5, tprev);
@@ -746,7 +760,7 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
           for (int n = 0; n < 4; n++)
             SMPC_COPY16_TO_LDS(lq + D::O_C + NA * NDX + 2 * (lane + NT * n), Cc + 2 * NT * n);
           SMPC_PLV(pf_dc) = lq[D::O_d + NA + (lane < NG ? lane : 0)];
-          SMPC_PLV(pf_ba) = lq[D::O_C + (lane < NA ? lane * NDX + 6 + lane : 0)]; // 1 if the box row is active
+          SMPC_PLV(pf_ba) = lq[D::O_box + (lane < NA ? lane : 0)]; // 1 if the box row is active
           SMPC_PLV(pf_bd) = lq[D::O_d + (lane < NA ? lane : 0)];
           if (t > 0)
             SMPC_PLV(f_pf) = lq[-(int)D::LQ_STRIDE + D::O_f + (lane < NDX ? lane : 0)]; // f of the next stage of the sweep
@@ -1044,11 +1058,11 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
                                                                                                                                     : idx < N_STAGE ? 9 : 10;
     }
     SMPC_HD static constexpr bool from_gains(int c) { return c == 0 || c == 1 || c == 9; }
-    // offset of the chunk's source: in the gains block (chunks 0, 1, 9) or in the LQ block (chunks 2 .. 7)
+    // offset of the chunk's source: in the gains block (chunks 0, 1, 9) or in the LQ block (chunks 2 .. 8; 8: the run of box selectors, Dims::O_box)
     SMPC_HD static constexpr int src(int c)
     {
       return c == 0 ? GK::G_W : c == 1 ? GK::G_pn : c == 9 ? GK::G_Pt : c == 2 ? D::O_A : c == 3 ? D::O_A + D::NV * NDX : c == 4 ? D::O_B
-             : c == 5 ? D::O_B + D::NV * NU : c == 6 ? D::O_C + D::NA * NDX : D::O_f;
+             : c == 5 ? D::O_B + D::NV * NU : c == 6 ? D::O_C + D::NA * NDX : c == 8 ? D::O_box : D::O_f;
     }
     double st[PER_EARLY * 64];
     double dx[NDX], du[NU], y[NDX], part[64], lpd_prev[NDX];
@@ -1090,10 +1104,8 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
           const int c = FL::chunk(lo);
           if (FL::from_gains(c))
             r[n] = g[FL::src(c) + lo - FL::start(c) + lane];
-          else if (c < 8)
+          else if (c <= 8)
             r[n] = lq[FL::src(c) + lo - FL::start(c) + lane];
-          else if (c == 8)
-            r[n] = lq[D::O_C + (lo + lane - FL::O_box) * (NDX + 1) + 6];
           else
             r[n] = 0.0;
         }
@@ -1106,10 +1118,7 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
           for (int c = 0; c < 10; c++)
           {
             const bool in = idx >= FL::start(c) && idx < FL::start(c + 1);
-            if (c == 8)
-              off = in ? D::O_C + (idx - FL::O_box) * (NDX + 1) + 6 : off;
-            else
-              off = in ? FL::src(c) + idx - FL::start(c) : off;
+            off = in ? FL::src(c) + idx - FL::start(c) : off;
             ing = (in && FL::from_gains(c)) ? true : ing;
           }
           const double * src = ing ? g + off : lq + off; // address select, ONE load, no wait on its value
@@ -1261,10 +1270,10 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
         double acc = lq[D::O_r + k];
 #pragma unroll 4
         for (int j = 0; j < NU; j++)
-          acc += lq[D::r_off(k, j)] * s.du[j];
+          acc += D::R_at(lq, b.lqc, k, j) * s.du[j];
 #pragma unroll 4
         for (int i = 0; i < NDX; i++)
-          acc += lq[D::s_off(i, k)] * s.dx[i];
+          acc += D::S_at(lq, b.lqc, i, k) * s.dx[i];
         SMPC_PLV(gpart) = acc;
       }
       SMPC_LANES_END_WAVE

@@ -244,10 +244,10 @@ namespace smpc
       SMPC_LANES(NT)
       {
         mm_tn<NDX, NXU, NDX, 3, 3, NT>(
-          s.AB, NXU, s.MT, NXU, lane, [&](int i, int j) { return j < NDX ? lq[D::q_off(i, j)] : lq[D::s_off(i, j - NDX)]; }, // (tile layout of the knot, Dims::O_T)
+          s.AB, NXU, s.MT, NXU, lane, [&](int i, int j) { return j < NDX ? lq[D::q_off(i, j)] : D::S_at(lq, b.lqc, i, j - NDX); }, // (tile layout of the knot, Dims::O_T; its last tile column: the handle's image)
           [&](int i, int j, double v) { s.QS[i * NXU + j] = v; });
         mm_tn<NU, NU, NDX, 3, 3, NT>(
-          s.AB + NDX, NXU, s.MT + NDX, NXU, lane, [&](int i, int j) { return lq[D::r_off(i, j)]; },
+          s.AB + NDX, NXU, s.MT + NDX, NXU, lane, [&](int i, int j) { return D::R_at(lq, b.lqc, i, j); },
           [&](int i, int j, double v) { s.Rh[i * NU + j] = v; });
         if (lane < NXU)
         {
@@ -274,10 +274,10 @@ namespace smpc
             s.kk[i] = -v;
         });
       SMPC_LANES_END
-      // load C (active rows) over [A|B]
+      // load C (active rows) over [A|B]; the box rows are synthesised from their selectors
       SMPC_LANES(NT)
       for (int idx = lane; idx < NC * NDX; idx += NT)
-        s.AB[idx] = lq[D::O_C + idx];
+        s.AB[idx] = D::C_at(lq, idx / NDX, idx % NDX);
       SMPC_LANES_END
       // P_t = Q^ - W^T W + C^T C / mu ;  p_t = q^ - W^T w_r + C^T d / mu
       SMPC_LANES(NT)
@@ -375,11 +375,10 @@ namespace smpc
         else if (lane < NU + NC)
         {
           const int r = lane - NU;
-          const double * Cr = lq + D::O_C + r * NDX;
           double acc = lq[D::O_d + r];
 #pragma unroll 4
           for (int j = 0; j < NDX; j++)
-            acc += Cr[j] * dx[j];
+            acc += D::C_at(lq, r, j) * dx[j];
           const double dnu = acc / mu;
           b.dvs[lt * NC + r] = dnu;
           // vpd (mu dnu - d) - d dnu

@@ -99,7 +99,7 @@ namespace smpc
       for (double * p : {buf.CN, buf.vN, buf.vN_e, buf.vN_b, buf.dvN, buf.dcm_ref, buf.es, buf.es_e, buf.es_b, buf.des, buf.ek, buf.ls, buf.ls_e, buf.ls_b, buf.dls, buf.lk})
         dev_free(p);
       for (double * p : {buf.xs_b, buf.us_b, buf.vs_b, buf.lams_b, buf.xs, buf.us, buf.vs, buf.lams, buf.vs_e, buf.lams_e, buf.dxs, buf.dus, buf.dvs, buf.dlams, buf.foot_ref, buf.ftraj,
-                         buf.vbase, buf.vref, buf.lq, buf.gains, buf.ev, buf.evd, buf.QN, buf.qN, buf.parts0, buf.partsT, buf.scal, buf.xdotT, buf.xdot01, buf.forces, buf.forcesT,
+                         buf.vbase, buf.vref, buf.lq, buf.lqc, buf.gains, buf.ev, buf.evd, buf.QN, buf.qN, buf.parts0, buf.partsT, buf.scal, buf.xdotT, buf.xdot01, buf.forces, buf.forcesT,
                          buf.dbg, X_dev})
         dev_free(p);
       dev_free(buf.ls_sel);
@@ -474,7 +474,7 @@ namespace smpc
       adv(s.dxs, (Hs + 1) * D::NDX); adv(s.dus, Hs * D::NU); adv(s.dvs, Hs * D::NC); adv(s.dlams, Hs * D::NDX);
       adv(s.foot_ref, Hs * D::NF * 3); adv(s.ftraj, (size_t)D::NF * 6); adv(s.vbase, 6); adv(s.vref, Rs * 6);
       s.ev_inst0 = b.ev_inst0 + i0;
-      adv(s.lq, Hs * D::LQ_STRIDE); adv(s.gains, Hs * gains_stride());
+      adv(s.lq, Hs * D::LQ_STRIDE); adv(s.gains, Hs * gains_stride()); // (lqc: one image for every part)
       adv(s.QN, (size_t)D::NDX * D::NDX); adv(s.qN, D::NDX);
       adv(s.parts0, (Hs + 1) * 4); adv(s.partsT, (size_t)D::LS_N * (Hs + 1) * 2); adv(s.scal, SC_N);
       adv(s.xdotT, (size_t)D::LS_N * 4 * D::NV); adv(s.xdot01, (size_t)4 * D::NV);
