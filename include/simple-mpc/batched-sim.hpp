@@ -150,6 +150,54 @@ namespace simple_mpc
     // the same as device pointers owned by the handle (they change when setGround is called again)
     void groundForceDevicePointers(double ** lambda_device, uint32_t ** contact_device) { check(smpc_robot_sim_get_ground_last(h_, lambda_device, contact_device)); }
 
+    // ---- per-robot slopes, friction and pushes on that ground (smpc_robot_sim_set_ground_env and the entries after it) ----
+    // planes [B][4] = (n, d): robot i stands on {p : n . p = d}, n a unit normal in world axes with n.z >= 0.5; mu [B] > 0.  An empty vector
+    // stands for the handle's setting for every robot ((0, 0, 1, ground_z), the mu of setGround); a call replaces both.  Needs setGround
+    // first; setGround called afterwards drops the per-robot ground and the push.
+    void setGroundEnv(const std::vector<double> & planes = {}, const std::vector<double> & mu = {})
+    {
+      if ((!planes.empty() && planes.size() != (size_t)batch_ * 4) || (!mu.empty() && mu.size() != (size_t)batch_))
+        throw std::runtime_error("planes [B][4], mu [B] expected (or empty)");
+      check(smpc_robot_sim_set_ground_env(h_, planes.empty() ? nullptr : planes.data(), mu.empty() ? nullptr : mu.data()));
+    }
+    // push [B][6] = (f, o): the force f (world axes, N) on the body of joint `joint` (0 = the base) at the point o given in that joint's
+    // frame; an empty vector clears the push
+    void setPush(const std::vector<double> & push = {}, int joint = 0)
+    {
+      if (!push.empty() && push.size() != (size_t)batch_ * 6)
+        throw std::runtime_error("push [B][6] expected (or empty)");
+      check(smpc_robot_sim_set_ground_push(h_, joint, push.empty() ? nullptr : push.data()));
+    }
+    // the handle-owned push buffer [B][6] on the device (null while no push is set): a resident loop may rewrite it on the shared stream;
+    // values written there are not validated
+    double * pushDevicePointer()
+    {
+      double * p = nullptr;
+      check(smpc_robot_sim_get_ground_push(h_, &p));
+      return p;
+    }
+    // groundDynamics with an explicit environment per state: planes [n][4], mu [n], push [n][6] (each may be empty: the handle's setting of
+    // setGround, no push); the handle's own environment is not read
+    GroundDynamics groundEnvDynamics(const std::vector<double> & X, const std::vector<double> & tau, double dt, const std::vector<double> & planes = {},
+                                     const std::vector<double> & mu = {}, const std::vector<double> & push = {}, int joint = 0)
+    {
+      const size_t nx = (size_t)(nq_ + nv_), n = X.size() / nx;
+      if (n == 0 || X.size() != n * nx || tau.size() != n * (size_t)(nv_ - 6))
+        throw std::runtime_error("X [n][nq + nv], tau [n][nv - 6] expected");
+      if ((!planes.empty() && planes.size() != n * 4) || (!mu.empty() && mu.size() != n) || (!push.empty() && push.size() != n * 6))
+        throw std::runtime_error("planes [n][4], mu [n], push [n][6] expected (or empty)");
+      GroundDynamics g;
+      g.v_next.resize(n * nv_);
+      g.a.resize(n * nv_);
+      g.lambda.resize(n * 3 * (size_t)gn_);
+      g.gap.resize(n * (size_t)gn_);
+      g.contact.resize(n);
+      check(smpc_robot_sim_ground_env_dynamics(h_, (int)n, X.data(), tau.data(), dt, planes.empty() ? nullptr : planes.data(), mu.empty() ? nullptr : mu.data(),
+                                               push.empty() ? nullptr : push.data(), joint, g.v_next.data(), g.a.data(), g.lambda.data(), g.gap.data(),
+                                               g.contact.data()));
+      return g;
+    }
+
   private:
     static void check(int rc)
     {

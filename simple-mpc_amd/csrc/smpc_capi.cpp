@@ -9,6 +9,7 @@
 #include "smpc_id_rt.h"
 #include "smpc_sim_rt.h"
 #include "smpc_sim_ground_rt.h"
+#include "smpc_sim_ground_env_rt.h"
 #include "smpc_robot_check.h"
 #include <atomic>
 #include <cstring>
@@ -34,6 +35,7 @@ struct smpc_robot_sim // stand-alone simulator handle: a robot table and nothing
 {
   std::unique_ptr<RobotSimRt> e;
   std::unique_ptr<RobotSimGround> g; // the ground plane, once smpc_robot_sim_set_ground has been called (destroyed before the engine it refers to)
+  std::unique_ptr<RobotSimGroundEnv> ge; // its per-robot environment and the staging of the host-buffer solve (destroyed before the ground it refers to)
 };
 
 struct smpc_handle
@@ -1290,6 +1292,7 @@ extern "C"
     return guarded([&] {
       sim->e->wait(); // (a step in flight still writes the buffers that are replaced below)
       std::unique_ptr<RobotSimGround> g(new RobotSimGround(*sim->e, settings));
+      sim->ge.reset(); // (the per-robot environment and the push go with the ground they were set on)
       sim->g = std::move(g);
     });
   }
@@ -1309,6 +1312,8 @@ extern "C"
       return fail(SMPC_ERR_INVALID, "smpc_robot_sim_step_ground_device: no ground yet, call smpc_robot_sim_set_ground first");
     if (!(dt > 0.0) || !std::isfinite(dt))
       return fail(SMPC_ERR_INVALID, "dt must be positive");
+    if (sim->ge && sim->ge->active) // (a per-robot environment or a push has been set: sim_ground_env_rt_body)
+      return guarded([&] { sim->ge->step_device(X_device, tau_device, dt); });
     return guarded([&] { sim->g->step_device(X_device, tau_device, dt); });
   }
   int smpc_robot_sim_ground_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, double * v_next_out, double * a_out,
@@ -1343,5 +1348,70 @@ extern "C"
     if (!sim->g)
       return fail(SMPC_ERR_INVALID, "smpc_robot_sim_read_ground_last: no ground yet, call smpc_robot_sim_set_ground first");
     return guarded([&] { sim->g->read_last(lambda_out, contact_out); });
+  }
+
+  // ---- per-robot planes, friction and pushes on the ground (smpc_sim_ground_env_rt.h) ----
+  int smpc_robot_sim_set_ground_env(smpc_robot_sim * sim, const double * plane, const double * mu)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_set_ground_env: no ground yet, call smpc_robot_sim_set_ground first");
+    // admission before anything else: nothing is allocated, and the previous environment stays, for values the model does not admit
+    const std::string why = sim_ground_env_admission_error(sim->e->B, plane, mu);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      if (!sim->ge)
+        sim->ge.reset(new RobotSimGroundEnv(*sim->g));
+      sim->ge->set_env(plane, mu);
+    });
+  }
+  int smpc_robot_sim_set_ground_push(smpc_robot_sim * sim, int push_joint, const double * push)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_set_ground_push: no ground yet, call smpc_robot_sim_set_ground first");
+    const std::string why = sim_ground_push_admission_error(sim->e->B, sim->e->sz.nq - 6, push_joint, push);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      if (!sim->ge)
+        sim->ge.reset(new RobotSimGroundEnv(*sim->g));
+      sim->ge->set_push(push_joint, push);
+    });
+  }
+  int smpc_robot_sim_get_ground_push(smpc_robot_sim * sim, double ** push_device)
+  {
+    if (!sim || !push_device)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_get_ground_push: no ground yet, call smpc_robot_sim_set_ground first");
+    *push_device = sim->ge ? sim->ge->push : nullptr;
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_ground_env_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const double * plane, const double * mu,
+                                         const double * push, int push_joint, double * v_next_out, double * a_out, double * lambda_out, double * gap_out,
+                                         uint32_t * contact_out)
+  {
+    if (!sim || !X || !tau)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_ground_env_dynamics: no ground yet, call smpc_robot_sim_set_ground first");
+    if (n < 1)
+      return fail(SMPC_ERR_INVALID, "n must be positive");
+    if (!(dt > 0.0) || !std::isfinite(dt))
+      return fail(SMPC_ERR_INVALID, "dt must be positive");
+    std::string why = sim_ground_env_admission_error(n, plane, mu);
+    if (why.empty())
+      why = sim_ground_push_admission_error(n, sim->e->sz.nq - 6, push_joint, push);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      if (!sim->ge)
+        sim->ge.reset(new RobotSimGroundEnv(*sim->g)); // (staging only: the handle's ground steps stay on sim_ground_rt_body until a setter is called)
+      sim->ge->dynamics(n, X, tau, dt, plane, mu, push, push_joint, v_next_out, a_out, lambda_out, gap_out, contact_out);
+    });
   }
 }

@@ -1651,6 +1651,58 @@ class BatchedRobotSim:
         self._lib.check(self._lib.L.smpc_robot_sim_get_ground_last(self._h, C.byref(lam), C.byref(con)))
         return int(lam.value), int(con.value)
 
+    # ---- per-robot slopes, friction and pushes on the ground (simple-mpc_amd/csrc/smpc_sim_ground_env_rt.h) ----
+    @staticmethod
+    def _env_array(v, shape, what):
+        if v is None:
+            return None
+        v = np.ascontiguousarray(np.array(v, dtype=np.float64))
+        if v.shape != shape:
+            raise RuntimeError("%s expected" % what)
+        return v
+
+    def setGroundEnv(self, planes=None, mu=None):
+        """Give every robot its own ground: planes [B, 4] = (n, d), the plane {p : n . p = d} with n a unit normal in world axes
+        (n.z >= 0.5), and friction coefficients mu [B] > 0.  None stands for the handle's setting for every robot ((0, 0, 1, ground_z),
+        the mu of setGround); a call replaces both.  Needs setGround first; setGround called afterwards drops the per-robot ground and
+        the push."""
+        pl = self._env_array(planes, (self.B, 4), "planes [B, 4]")
+        m = self._env_array(mu, (self.B,), "mu [B]")
+        p = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)
+        self._lib.check(self._lib.L.smpc_robot_sim_set_ground_env(self._h, p(pl), p(m)))
+
+    def setPush(self, push=None, joint=0):
+        """One external force per robot: push [B, 6] = (f, o), the force f (world axes, N) acting on the body of joint `joint` (one index
+        per handle, 0 = the base) at the point o given in that joint's frame.  None clears the push."""
+        ps = self._env_array(push, (self.B, 6), "push [B, 6]")
+        self._lib.check(self._lib.L.smpc_robot_sim_set_ground_push(self._h, int(joint), None if ps is None else ps.ctypes.data_as(C.c_void_p)))
+
+    def pushDevicePointer(self):
+        """The device pointer of the handle-owned push buffer [B][6] (0 while no push is set): a resident loop may rewrite the pushes on
+        the shared stream.  Values written there are not validated."""
+        ptr = C.c_void_p()
+        self._lib.check(self._lib.L.smpc_robot_sim_get_ground_push(self._h, C.byref(ptr)))
+        return int(ptr.value or 0)
+
+    def groundEnvDynamics(self, X, tau, dt, planes=None, mu=None, push=None, joint=0):
+        """groundDynamics with an explicit environment per state: planes [n, 4], mu [n], push [n, 6] (None: the handle's setting of
+        setGround, no push) and the push joint.  n need not be the batch, nothing is advanced and the handle's own environment is not
+        read.  Returns the dict of groundDynamics; lam in world axes, gap = n . p - d."""
+        X = np.ascontiguousarray(np.array(X, dtype=np.float64))
+        tau = np.ascontiguousarray(np.array(tau, dtype=np.float64))
+        n = X.shape[0] if X.ndim == 2 else 0
+        if n < 1 or X.shape[1] != self.nq + self.nv or tau.shape != (n, self.nv - 6):
+            raise RuntimeError("X [n, nq + nv], tau [n, nv - 6] expected")
+        pl = self._env_array(planes, (n, 4), "planes [n, 4]")
+        m = self._env_array(mu, (n,), "mu [n]")
+        ps = self._env_array(push, (n, 6), "push [n, 6]")
+        p = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)
+        npts = self._ground_npts()
+        v, a, lam, gap, con = np.zeros((n, self.nv)), np.zeros((n, self.nv)), np.zeros((n, 3 * npts)), np.zeros((n, npts)), np.zeros(n, np.uint32)
+        self._lib.check(self._lib.L.smpc_robot_sim_ground_env_dynamics(self._h, n, X, tau, float(dt), p(pl), p(m), p(ps), int(joint), v.ctypes.data,
+                                                                       a.ctypes.data, lam.ctypes.data, gap.ctypes.data, con.ctypes.data))
+        return dict(v_next=v, a=a, lam=lam, gap=gap, contact=con)
+
 
 class FrictionCompensation:
     """reference include/simple-mpc/friction-compensation.hpp: torque += viscuous * v + dry * sign(v).  The reference reads

@@ -172,6 +172,7 @@ SYMBOLS = [
     "smpc_id_create", "smpc_id_create_any", "smpc_id_destroy", "smpc_id_set_target", "smpc_id_set_targets", "smpc_id_set_target_centroidal", "smpc_id_set_targets_centroidal", "smpc_id_solve", "smpc_id_solve_device", "smpc_id_wait", "smpc_id_get_resid", "smpc_id_reset", "smpc_id_get_tau_device", "smpc_id_get_x_device", "smpc_id_set_targets_from_mpc", "smpc_id_share_stream", "smpc_sim_step_device", "smpc_id_debug_get", "smpc_id_get_dims", "smpc_debug_id_force_rt",
     "smpc_robot_sim_create", "smpc_robot_sim_destroy", "smpc_robot_sim_get_dims", "smpc_robot_sim_wait", "smpc_robot_sim_get_stream", "smpc_robot_sim_share_stream", "smpc_robot_sim_forward_dynamics", "smpc_robot_sim_step_device", "smpc_robot_sim_get_last", "smpc_robot_sim_read_last",
     "smpc_robot_sim_set_ground", "smpc_robot_sim_get_ground_dims", "smpc_robot_sim_step_ground_device", "smpc_robot_sim_ground_dynamics", "smpc_robot_sim_get_ground_last", "smpc_robot_sim_read_ground_last",
+    "smpc_robot_sim_set_ground_env", "smpc_robot_sim_set_ground_push", "smpc_robot_sim_get_ground_push", "smpc_robot_sim_ground_env_dynamics",
 ]
 
 
@@ -314,6 +315,10 @@ class SmpcLib:
         L.smpc_robot_sim_ground_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, vp, vp, vp, vp, vp]
         L.smpc_robot_sim_get_ground_last.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.smpc_robot_sim_read_ground_last.argtypes = [vp, vp, vp]
+        L.smpc_robot_sim_set_ground_env.argtypes = [vp, vp, vp]
+        L.smpc_robot_sim_set_ground_push.argtypes = [vp, C.c_int, vp]
+        L.smpc_robot_sim_get_ground_push.argtypes = [vp, C.POINTER(vp)]
+        L.smpc_robot_sim_ground_env_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
 
     def check(self, code):
         if code < 0:

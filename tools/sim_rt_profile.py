@@ -18,7 +18,16 @@ The ground plane, same method:
 `run-ground`: per robot of GROUND_RUNS BatchedRobotSim.stepDevice (sim_rt_body, every foot in contact: the yardstick of the same run), then
 stepGroundDevice with the plane at the reference foot height on both instantiations (a points-per-foot count that gives at most 12 rows,
 one that gives more) at each of GROUND_SWEEPS sweeps.  `summary-ground`: one row per run, and the cost of a sweep as the slope between
-the smallest and the largest sweep count."""
+the smallest and the largest sweep count.
+
+The per-robot environment, same method:
+
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -o env -- python3 tools/sim_rt_profile.py run-env [batch]
+    python3 tools/sim_rt_profile.py summary-env <kernel_trace.csv> [batch]
+
+`run-env`: per robot of GROUND_RUNS, instantiation and sweep count stepGroundDevice on a handle without an environment (sim_ground_rt_body:
+the yardstick of the same run), then on the same handle after setGroundEnv / setPush with the uniform environment (sim_ground_env_rt_body:
+the same answers bit for bit).  `summary-env`: both columns, their ratio, the cost of a sweep and the intercept at zero sweeps of each."""
 import collections
 import csv
 import os
@@ -97,6 +106,72 @@ def run_ground(B):
             print(name, kind, "P", P, "sweeps", sw, "finite:", bool(np.isfinite(Xh).all()), "largest state change %.3f" % np.abs(Xh - X).max() + note, flush=True)
 
 
+def run_env(B):
+    sys.path[:0] = [os.path.join(ROOT, "simple-mpc_amd", "python"), os.path.join(ROOT, "tests")]
+    import numpy as np
+    import torch
+    import robot_tables as RT
+    import simple_mpc
+    import test_id_any_robot as T
+
+    for name, fs, p12, p24 in GROUND_RUNS:
+        tab = T.table(name)
+        rb = RT.oracle_robot(tab)
+        sim = simple_mpc.BatchedRobotSim(RT.model_handler(tab), force_size=fs, batch=B)
+        gz = float(rb.centroidal(rb.x_ref)["feet"][:, 2].min())
+        X = RT.near_reference_states(rb, min(B, 64), seed=5, scale=0.3)
+        X = np.tile(X, (-(-B // X.shape[0]), 1))[:B]
+        td = torch.from_numpy(np.random.default_rng(6).normal(0.0, 1.0, (B, rb.nv - 6))).cuda()
+        for P in (p12, p24):
+            for sw in GROUND_SWEEPS:
+                ends = []
+                for env in (False, True):
+                    sim.setGround(ground_z=gz, points=GROUND_POINTS[P], sweeps=sw)  # (drops the environment of the run before)
+                    if env:
+                        sim.setGroundEnv(planes=np.tile([0.0, 0.0, 1.0, gz], (B, 1)), mu=np.full(B, 0.7))
+                        sim.setPush(np.zeros((B, 6)))
+                    Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
+                    torch.cuda.synchronize()
+                    for _ in range(WARM + READINGS * LAUNCHES):
+                        sim.stepGroundDevice(Xd.data_ptr(), td.data_ptr(), 1e-3)
+                    sim.wait()
+                    ends.append(Xd.cpu().numpy())
+                print(name, "P", P, "sweeps", sw, "finite:", bool(np.isfinite(ends[0]).all()), "the two kernels agree bit for bit:", bool(np.array_equal(ends[0], ends[1])),
+                      flush=True)
+
+
+def summary_env(trace, B):
+    d = []  # (kernel, duration) in launch order
+    for r in sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"])):
+        grid = int(r["Grid_Size"]) if "Grid_Size" in r else int(r["Grid_Size_X"])
+        m = re.search(r"(sim_ground_rt_body|sim_ground_env_rt_body)(?:<|ILi)(\d+)", r["Kernel_Name"])
+        if m and grid == B * 64:
+            d.append(("%s<%s>" % m.groups(), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3))
+    per = WARM + READINGS * LAUNCHES
+    assert len(d) == per * len(GROUND_RUNS) * 2 * len(GROUND_SWEEPS) * 2, len(d)
+    print("| robot | rows | points | sweeps | `sim_ground_rt_body` µs (spread) | `sim_ground_env_rt_body` µs (spread) | ratio |")
+    print("|---|---|---|---|---|---|---|")
+    k = 0
+    for name, fs, p12, p24 in GROUND_RUNS:
+        for P in (p12, p24):
+            cols = ([], [])
+            for sw in GROUND_SWEEPS:
+                cell = []
+                for env in (0, 1):
+                    blk = d[k * per: (k + 1) * per]
+                    k += 1
+                    assert len(set(n for n, _ in blk)) == 1 and ("env" in blk[0][0]) == bool(env), set(n for n, _ in blk)
+                    t = [v for _, v in blk[WARM:]]
+                    means = [sum(t[i * LAUNCHES: (i + 1) * LAUNCHES]) / LAUNCHES for i in range(READINGS)]
+                    cols[env].append(min(means))
+                    cell.append("%.1f (%.1f %%)" % (min(means), 100 * (max(means) / min(means) - 1.0)))
+                print("| %s | %s | %d | %d | %s | %s | %.3f |" % (name, blk[0][0][-3:-1], P * T_NFEET[name], sw, cell[0], cell[1], cols[1][-1] / cols[0][-1]))
+            span = GROUND_SWEEPS[-1] - GROUND_SWEEPS[0]
+            slopes = [(c[-1] - c[0]) / span for c in cols]
+            print("| %s |  | %d | per sweep / intercept | %.2f / %.1f | %.2f / %.1f | |"
+                  % (name, P * T_NFEET[name], slopes[0], cols[0][0] - GROUND_SWEEPS[0] * slopes[0], slopes[1], cols[1][0] - GROUND_SWEEPS[0] * slopes[1]))
+
+
 def summary_ground(trace, B):
     d = []  # (kernel, rows of the instantiation, duration) in launch order
     for r in sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"])):
@@ -164,6 +239,10 @@ if __name__ == "__main__":
         run(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     elif sys.argv[1] == "run-ground":
         run_ground(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+    elif sys.argv[1] == "run-env":
+        run_env(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+    elif sys.argv[1] == "summary-env":
+        summary_env(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 4096)
     elif sys.argv[1] == "summary-ground":
         summary_ground(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 4096)
     else:
