@@ -198,6 +198,76 @@ namespace simple_mpc
       return g;
     }
 
+    // ---- warm-started contact solve with a stopping rule on that ground (smpc_robot_sim_set_ground_solver and the entries after it) ----
+    // warm_start: every robot starts its sweeps from its own forces of the previous step (the handle-owned warm buffer, contact frame);
+    // tol > 0 (m/s): a robot's sweeps stop after sweep s >= min_sweeps once rho_s <= tol (tol = 0: exactly `sweeps` sweeps; min_sweeps in
+    // 1 .. sweeps, 0 stands for 1).  Zeroes the warm buffer.  Needs setGround first; setGround called afterwards drops the settings.
+    void setGroundSolver(bool warm_start = false, double tol = 0.0, int min_sweeps = 0)
+    {
+      const smpc_ground_solver_settings s = {warm_start ? 1 : 0, tol, min_sweeps};
+      check(smpc_robot_sim_set_ground_solver(h_, &s));
+    }
+    // zero the warm rows of the listed robots (an empty list: every robot); asynchronous on the handle's stream
+    void resetGroundWarmStart(const std::vector<int> & indices = {})
+    {
+      check(smpc_robot_sim_reset_ground_warm_start(h_, indices.empty() ? nullptr : indices.data(), (int)indices.size()));
+    }
+    // the same for every robot with a non-zero byte in mask_device [B] (device memory)
+    void resetGroundWarmStartDevice(const uint8_t * mask_device) { check(smpc_robot_sim_reset_ground_warm_start_device(h_, mask_device)); }
+    // sweeps run [B] / rho of the last sweep run [B] in the last ground step (host copies; join the handle's stream)
+    std::vector<int32_t> lastGroundSweeps()
+    {
+      std::vector<int32_t> s((size_t)batch_);
+      check(smpc_robot_sim_read_ground_solver_last(h_, s.data(), nullptr));
+      return s;
+    }
+    std::vector<double> lastGroundResiduals()
+    {
+      std::vector<double> r((size_t)batch_);
+      check(smpc_robot_sim_read_ground_solver_last(h_, nullptr, r.data()));
+      return r;
+    }
+    // the same and the warm buffer [B][3 points] as device pointers owned by the handle (they change when setGround is called again)
+    void groundSolverDevicePointers(int32_t ** sweeps_device, double ** residual_device, double ** warm_device)
+    {
+      check(smpc_robot_sim_get_ground_solver_last(h_, sweeps_device, residual_device, warm_device));
+    }
+    struct GroundSolve
+    {
+      GroundDynamics g;
+      std::vector<double> lambda_contact, residual; // [n][3 points] in the contact frame [point][t1 t2 n], [n]
+      std::vector<int32_t> sweeps;                  // [n]
+    };
+    // groundEnvDynamics with explicit solver settings and an explicit start vector lam0 [n][3 points] in the contact frame (empty: zeros;
+    // read only if warm_start); the handle's settings and warm buffer are neither read nor changed
+    GroundSolve groundSolveDynamics(const std::vector<double> & X, const std::vector<double> & tau, double dt, const std::vector<double> & planes = {},
+                                    const std::vector<double> & mu = {}, const std::vector<double> & push = {}, int joint = 0, const std::vector<double> & lam0 = {},
+                                    bool warm_start = true, double tol = 0.0, int min_sweeps = 0)
+    {
+      const size_t nx = (size_t)(nq_ + nv_), n = X.size() / nx, nr = 3 * (size_t)gn_;
+      if (n == 0 || X.size() != n * nx || tau.size() != n * (size_t)(nv_ - 6))
+        throw std::runtime_error("X [n][nq + nv], tau [n][nv - 6] expected");
+      if ((!planes.empty() && planes.size() != n * 4) || (!mu.empty() && mu.size() != n) || (!push.empty() && push.size() != n * 6))
+        throw std::runtime_error("planes [n][4], mu [n], push [n][6] expected (or empty)");
+      if (!lam0.empty() && lam0.size() != n * nr)
+        throw std::runtime_error("lam0 [n][3 points] expected (or empty)");
+      const smpc_ground_solver_settings s = {warm_start && !lam0.empty() ? 1 : 0, tol, min_sweeps};
+      GroundSolve r;
+      r.g.v_next.resize(n * nv_);
+      r.g.a.resize(n * nv_);
+      r.g.lambda.resize(n * nr);
+      r.g.gap.resize(n * (size_t)gn_);
+      r.g.contact.resize(n);
+      r.lambda_contact.resize(n * nr);
+      r.residual.resize(n);
+      r.sweeps.resize(n);
+      check(smpc_robot_sim_ground_solve_dynamics(h_, (int)n, X.data(), tau.data(), dt, planes.empty() ? nullptr : planes.data(), mu.empty() ? nullptr : mu.data(),
+                                                 push.empty() ? nullptr : push.data(), joint, &s, lam0.empty() ? nullptr : lam0.data(), r.g.v_next.data(),
+                                                 r.g.a.data(), r.g.lambda.data(), r.lambda_contact.data(), r.g.gap.data(), r.g.contact.data(), r.sweeps.data(),
+                                                 r.residual.data()));
+      return r;
+    }
+
   private:
     static void check(int rc)
     {

@@ -654,6 +654,53 @@ int smpc_robot_sim_ground_env_dynamics(smpc_robot_sim * sim, int n, const double
                                        const double * push, int push_joint, double * v_next_out, double * a_out, double * lambda_out, double * gap_out,
                                        uint32_t * contact_out);
 
+/* ---- warm-started contact solve with a stopping rule on that ground (simple-mpc_amd/csrc/smpc_sim_ground_ws_rt.h) ----
+ * After smpc_robot_sim_set_ground every robot runs exactly `sweeps` sweeps of projected Gauss-Seidel from lambda = 0.  The entries below let
+ * robot i start from its own forces of the previous step, stop when a sweep has stopped moving them, and report how far it got.
+ *   start    lambda0_r = w[i][r] if warm_start is set and w[i][r] is finite, else 0.  w is the handle-owned warm buffer [B][3 points], laid out
+ *            IN THE CONTACT FRAME, [point][t1 t2 n], so a slope needs no rotation; an entry that is not finite reads as 0.
+ *   sweeps   s = 1 .. sweeps as before; sweep s also yields rho_s = max_r |lambda_r(new) - lambda_r(old)| dt G_rr (m/s) over the robot's rows,
+ *            `old` the row's value before the sweep touches it, `new` the value written (after the projection for tangential rows).
+ *   stop     after sweep s if tol > 0, s >= min_sweeps and rho_s <= tol.  tol = 0: exactly `sweeps` sweeps.  A NaN rho never stops.
+ *   outputs  per robot sweeps_used (int32) and residual (rho of the last sweep run); on a step, w[i] <- lambda in the contact frame.
+ * Each entry needs smpc_robot_sim_set_ground first, validates before it allocates, answers SMPC_ERR_INVALID with a message that names the
+ * field and leaves the previous settings in force.
+ *   smpc_robot_sim_set_ground_solver   warm_start 0 / 1; tol >= 0 finite; min_sweeps in 1 .. sweeps of the ground (0 stands for 1).  Zeroes
+ *                            the warm buffer; joins the handle's stream first.  From this call on smpc_robot_sim_step_ground_device
+ *                            launches sim_ground_ws_rt_body, which reads the per-robot environment and push if they are set.  With
+ *                            {0, 0, 0} the results equal those of the kernels above bit for bit.
+ *   smpc_robot_sim_set_ground          (above) called afterwards DROPS the solver settings and the warm buffer, as it drops the environment.
+ *   smpc_robot_sim_reset_ground_warm_start   zeroes the warm rows of the n robots of a host list (unsorted, duplicates allowed; an index
+ *                            outside 0 .. B - 1 refuses the whole call); n = 0 resets every robot.  Asynchronous on the handle's stream.
+ *   smpc_robot_sim_reset_ground_warm_start_device   the same for every robot with a non-zero byte in mask_device [B] (device memory), one
+ *                            kernel on the handle's stream, no host round trip.
+ *   smpc_robot_sim_get_ground_solver_last   device pointers of sweeps_used [B], residual [B] and the warm buffer [B][3 points] (owned by the
+ *                            handle; they change when smpc_robot_sim_set_ground is called again; NULL before the setter or the first
+ *                            smpc_robot_sim_ground_solve_dynamics: a getter allocates nothing); any output may be NULL.
+ *   smpc_robot_sim_read_ground_solver_last  sweeps_used and residual of the last ground step copied to host buffers (either may be NULL);
+ *                            joins the handle's stream.  Zeros before the first step after the setter (before the setter without
+ *                            touching the device).  The resets are no-ops that succeed while there is no warm buffer.
+ *   smpc_robot_sim_ground_solve_dynamics  smpc_robot_sim_ground_env_dynamics with explicit solver settings (NULL: {0, 0, 0}) and an
+ *                            explicit start vector lambda0 [n][3 points] in the contact frame (NULL: zeros; read only if
+ *                            settings->warm_start is set).  Further outputs lambda_contact_out [n][3 points] (contact frame),
+ *                            sweeps_out [n], residual_out [n]; any output may be NULL.  The handle's settings and warm buffer are neither
+ *                            read nor changed. */
+typedef struct smpc_ground_solver_settings
+{
+  int warm_start;
+  double tol;
+  int min_sweeps;
+} smpc_ground_solver_settings;
+int smpc_robot_sim_set_ground_solver(smpc_robot_sim * sim, const smpc_ground_solver_settings * settings);
+int smpc_robot_sim_reset_ground_warm_start(smpc_robot_sim * sim, const int * indices, int n);
+int smpc_robot_sim_reset_ground_warm_start_device(smpc_robot_sim * sim, const uint8_t * mask_device);
+int smpc_robot_sim_get_ground_solver_last(smpc_robot_sim * sim, int32_t ** sweeps_device, double ** residual_device, double ** warm_device);
+int smpc_robot_sim_read_ground_solver_last(smpc_robot_sim * sim, int32_t * sweeps_out, double * residual_out);
+int smpc_robot_sim_ground_solve_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const double * plane, const double * mu,
+                                         const double * push, int push_joint, const smpc_ground_solver_settings * settings, const double * lambda0,
+                                         double * v_next_out, double * a_out, double * lambda_out, double * lambda_contact_out, double * gap_out,
+                                         uint32_t * contact_out, int32_t * sweeps_out, double * residual_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@
 #include "smpc_sim_rt.h"
 #include "smpc_sim_ground_rt.h"
 #include "smpc_sim_ground_env_rt.h"
+#include "smpc_sim_ground_ws_rt.h"
 #include "smpc_robot_check.h"
 #include <atomic>
 #include <cstring>
@@ -36,6 +37,7 @@ struct smpc_robot_sim // stand-alone simulator handle: a robot table and nothing
   std::unique_ptr<RobotSimRt> e;
   std::unique_ptr<RobotSimGround> g; // the ground plane, once smpc_robot_sim_set_ground has been called (destroyed before the engine it refers to)
   std::unique_ptr<RobotSimGroundEnv> ge; // its per-robot environment and the staging of the host-buffer solve (destroyed before the ground it refers to)
+  std::unique_ptr<RobotSimGroundWs> gw;  // its solver settings, warm buffer and read-outs (destroyed before the ground it refers to)
 };
 
 struct smpc_handle
@@ -1293,6 +1295,7 @@ extern "C"
       sim->e->wait(); // (a step in flight still writes the buffers that are replaced below)
       std::unique_ptr<RobotSimGround> g(new RobotSimGround(*sim->e, settings));
       sim->ge.reset(); // (the per-robot environment and the push go with the ground they were set on)
+      sim->gw.reset(); // (and so do the solver settings and the warm buffer)
       sim->g = std::move(g);
     });
   }
@@ -1312,6 +1315,8 @@ extern "C"
       return fail(SMPC_ERR_INVALID, "smpc_robot_sim_step_ground_device: no ground yet, call smpc_robot_sim_set_ground first");
     if (!(dt > 0.0) || !std::isfinite(dt))
       return fail(SMPC_ERR_INVALID, "dt must be positive");
+    if (sim->gw && sim->gw->active) // (solver settings have been set: sim_ground_ws_rt_body, which reads the environment if there is one)
+      return guarded([&] { sim->gw->step_device(X_device, tau_device, dt, sim->ge.get()); });
     if (sim->ge && sim->ge->active) // (a per-robot environment or a push has been set: sim_ground_env_rt_body)
       return guarded([&] { sim->ge->step_device(X_device, tau_device, dt); });
     return guarded([&] { sim->g->step_device(X_device, tau_device, dt); });
@@ -1412,6 +1417,111 @@ extern "C"
       if (!sim->ge)
         sim->ge.reset(new RobotSimGroundEnv(*sim->g)); // (staging only: the handle's ground steps stay on sim_ground_rt_body until a setter is called)
       sim->ge->dynamics(n, X, tau, dt, plane, mu, push, push_joint, v_next_out, a_out, lambda_out, gap_out, contact_out);
+    });
+  }
+
+  // ---- warm-started contact solve with a stopping rule (smpc_sim_ground_ws_rt.h) ----
+  int smpc_robot_sim_set_ground_solver(smpc_robot_sim * sim, const smpc_ground_solver_settings * settings)
+  {
+    if (!sim || !settings)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_set_ground_solver: no ground yet, call smpc_robot_sim_set_ground first");
+    // admission before anything else: nothing is allocated, and the previous settings and the warm buffer stay, for settings the model does not admit
+    const std::string why = sim_ground_ws_admission_error(sim->g->gs.sweeps, settings);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      if (!sim->gw)
+        sim->gw.reset(new RobotSimGroundWs(*sim->g));
+      sim->gw->set_solver(settings);
+    });
+  }
+  int smpc_robot_sim_reset_ground_warm_start(smpc_robot_sim * sim, const int * indices, int n)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_reset_ground_warm_start: no ground yet, call smpc_robot_sim_set_ground first");
+    std::vector<unsigned char> m((size_t)sim->e->B);
+    const std::string why = sim_ground_ws_reset_error(indices, n, sim->e->B, m.data());
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    if (!sim->gw) // (no warm buffer before the setter: nothing to zero, nothing allocated)
+      return SMPC_OK;
+    return guarded([&] { sim->gw->reset_list(m); });
+  }
+  int smpc_robot_sim_reset_ground_warm_start_device(smpc_robot_sim * sim, const uint8_t * mask_device)
+  {
+    if (!sim || !mask_device)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_reset_ground_warm_start_device: no ground yet, call smpc_robot_sim_set_ground first");
+    if (!sim->gw)
+      return SMPC_OK;
+    return guarded([&] { sim->gw->reset_device(mask_device); });
+  }
+  int smpc_robot_sim_get_ground_solver_last(smpc_robot_sim * sim, int32_t ** sweeps_device, double ** residual_device, double ** warm_device)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_get_ground_solver_last: no ground yet, call smpc_robot_sim_set_ground first");
+    // (null pointers before the setter or the first host-buffer solve: a getter allocates nothing)
+    if (sweeps_device)
+      *sweeps_device = sim->gw ? sim->gw->sweeps : nullptr;
+    if (residual_device)
+      *residual_device = sim->gw ? sim->gw->resid : nullptr;
+    if (warm_device)
+      *warm_device = sim->gw ? sim->gw->warm : nullptr;
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_read_ground_solver_last(smpc_robot_sim * sim, int32_t * sweeps_out, double * residual_out)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_read_ground_solver_last: no ground yet, call smpc_robot_sim_set_ground first");
+    if (!sim->gw) // (zeros before the setter, without allocating or joining the stream)
+    {
+      for (int i = 0; i < sim->e->B; i++)
+      {
+        if (sweeps_out)
+          sweeps_out[i] = 0;
+        if (residual_out)
+          residual_out[i] = 0.0;
+      }
+      return SMPC_OK;
+    }
+    return guarded([&] { sim->gw->read_last(sweeps_out, residual_out); });
+  }
+  int smpc_robot_sim_ground_solve_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const double * plane, const double * mu,
+                                           const double * push, int push_joint, const smpc_ground_solver_settings * settings, const double * lambda0,
+                                           double * v_next_out, double * a_out, double * lambda_out, double * lambda_contact_out, double * gap_out,
+                                           uint32_t * contact_out, int32_t * sweeps_out, double * residual_out)
+  {
+    if (!sim || !X || !tau)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_ground_solve_dynamics: no ground yet, call smpc_robot_sim_set_ground first");
+    if (n < 1)
+      return fail(SMPC_ERR_INVALID, "n must be positive");
+    if (!(dt > 0.0) || !std::isfinite(dt))
+      return fail(SMPC_ERR_INVALID, "dt must be positive");
+    const smpc_ground_solver_settings inert = {0, 0.0, 0};
+    const smpc_ground_solver_settings * st = settings ? settings : &inert;
+    std::string why = sim_ground_ws_admission_error(sim->g->gs.sweeps, st);
+    if (why.empty())
+      why = sim_ground_env_admission_error(n, plane, mu);
+    if (why.empty())
+      why = sim_ground_push_admission_error(n, sim->e->sz.nq - 6, push_joint, push);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      if (!sim->gw)
+        sim->gw.reset(new RobotSimGroundWs(*sim->g)); // (staging only: the handle's ground steps keep their kernel until the setter is called)
+      sim->gw->dynamics(n, X, tau, dt, plane, mu, push, push_joint, sim_ground_ws_resolve(st), lambda0, v_next_out, a_out, lambda_out, lambda_contact_out,
+                        gap_out, contact_out, sweeps_out, residual_out);
     });
   }
 }

@@ -1703,6 +1703,74 @@ class BatchedRobotSim:
                                                                        a.ctypes.data, lam.ctypes.data, gap.ctypes.data, con.ctypes.data))
         return dict(v_next=v, a=a, lam=lam, gap=gap, contact=con)
 
+    # ---- warm-started contact solve with a stopping rule (simple-mpc_amd/csrc/smpc_sim_ground_ws_rt.h) ----
+    @staticmethod
+    def _solver_settings(warm_start, tol, min_sweeps):
+        s = _capi.GroundSolverSettingsC()
+        s.warm_start, s.tol, s.min_sweeps = int(bool(warm_start)), float(tol), int(min_sweeps)
+        return s
+
+    def setGroundSolver(self, warm_start=False, tol=0.0, min_sweeps=0):
+        """Solver settings of the ground's projected Gauss-Seidel: with warm_start every robot starts from its own forces of the previous
+        step (the handle-owned warm buffer, contact frame); with tol > 0 (m/s) a robot's sweeps stop after sweep s >= min_sweeps once
+        rho_s = max_r |change of lambda_r| dt G_rr <= tol (tol = 0: exactly `sweeps` sweeps; min_sweeps in 1 .. sweeps, 0 stands for 1).
+        Zeroes the warm buffer.  Needs setGround first; setGround called afterwards drops the settings and the buffer.  From this call on
+        stepGroundDevice reports lastGroundSweeps() and lastGroundResiduals()."""
+        s = self._solver_settings(warm_start, tol, min_sweeps)
+        self._lib.check(self._lib.L.smpc_robot_sim_set_ground_solver(self._h, C.byref(s)))
+
+    def resetGroundWarmStart(self, indices=None):
+        """Zero the warm rows of the listed robots (None or an empty list: every robot).  Asynchronous on the handle's stream."""
+        idx = np.ascontiguousarray(np.array([] if indices is None else indices, dtype=np.int32).reshape(-1))
+        self._lib.check(self._lib.L.smpc_robot_sim_reset_ground_warm_start(self._h, idx.ctypes.data_as(C.c_void_p) if idx.size else None, int(idx.size)))
+
+    def resetGroundWarmStartDevice(self, mask_ptr):
+        """The same for every robot with a non-zero byte in a uint8 mask [B] in device memory: one kernel on the handle's stream."""
+        self._lib.check(self._lib.L.smpc_robot_sim_reset_ground_warm_start_device(self._h, C.c_void_p(int(mask_ptr))))
+
+    def lastGroundSweeps(self):
+        """Sweeps run per robot [B] (int32) in the last ground step (host copy; joins the handle's stream)."""
+        sw = np.zeros(self.B, np.int32)
+        self._lib.check(self._lib.L.smpc_robot_sim_read_ground_solver_last(self._h, sw.ctypes.data, None))
+        return sw
+
+    def lastGroundResiduals(self):
+        """rho of the last sweep run per robot [B] (m/s) in the last ground step (host copy; joins the handle's stream)."""
+        r = np.zeros(self.B)
+        self._lib.check(self._lib.L.smpc_robot_sim_read_ground_solver_last(self._h, None, r.ctypes.data))
+        return r
+
+    def groundSolverDevicePointers(self):
+        """(sweeps_used [B] int32, residual [B], warm buffer [B][3 points] in the contact frame) as device pointers owned by the handle;
+        they change when setGround is called again; zeros before setGroundSolver or the first groundSolveDynamics."""
+        sw, r, w = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._lib.check(self._lib.L.smpc_robot_sim_get_ground_solver_last(self._h, C.byref(sw), C.byref(r), C.byref(w)))
+        return int(sw.value or 0), int(r.value or 0), int(w.value or 0)
+
+    def groundSolveDynamics(self, X, tau, dt, planes=None, mu=None, push=None, joint=0, lam0=None, warm_start=None, tol=0.0, min_sweeps=0):
+        """groundEnvDynamics with explicit solver settings and an explicit start vector lam0 [n, 3 points] in the contact frame (None:
+        zeros).  warm_start None stands for "lam0 is given"; with warm_start False lam0 is not read.  The settings come from the arguments
+        alone and the handle's warm buffer is neither read nor changed.  Returns the dict of groundEnvDynamics and lam_contact [n, 3 points]
+        (contact frame, [point][t1 t2 n]), sweeps [n] (int32), residual [n]."""
+        X = np.ascontiguousarray(np.array(X, dtype=np.float64))
+        tau = np.ascontiguousarray(np.array(tau, dtype=np.float64))
+        n = X.shape[0] if X.ndim == 2 else 0
+        if n < 1 or X.shape[1] != self.nq + self.nv or tau.shape != (n, self.nv - 6):
+            raise RuntimeError("X [n, nq + nv], tau [n, nv - 6] expected")
+        npts = self._ground_npts()
+        pl = self._env_array(planes, (n, 4), "planes [n, 4]")
+        m = self._env_array(mu, (n,), "mu [n]")
+        ps = self._env_array(push, (n, 6), "push [n, 6]")
+        l0 = self._env_array(lam0, (n, 3 * npts), "lam0 [n, 3 points]")
+        s = self._solver_settings(l0 is not None if warm_start is None else warm_start, tol, min_sweeps)
+        p = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)
+        v, a, lam, lamc, gap = np.zeros((n, self.nv)), np.zeros((n, self.nv)), np.zeros((n, 3 * npts)), np.zeros((n, 3 * npts)), np.zeros((n, npts))
+        con, sw, res = np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros(n)
+        self._lib.check(self._lib.L.smpc_robot_sim_ground_solve_dynamics(self._h, n, X, tau, float(dt), p(pl), p(m), p(ps), int(joint), C.byref(s), p(l0),
+                                                                         v.ctypes.data, a.ctypes.data, lam.ctypes.data, lamc.ctypes.data, gap.ctypes.data,
+                                                                         con.ctypes.data, sw.ctypes.data, res.ctypes.data))
+        return dict(v_next=v, a=a, lam=lam, gap=gap, contact=con, lam_contact=lamc, sweeps=sw, residual=res)
+
 
 class FrictionCompensation:
     """reference include/simple-mpc/friction-compensation.hpp: torque += viscuous * v + dry * sign(v).  The reference reads

@@ -158,6 +158,14 @@ class GroundSettingsC(C.Structure):  # smpc_ground_settings
     ]
 
 
+class GroundSolverSettingsC(C.Structure):  # smpc_ground_solver_settings
+    _fields_ = [
+        ("warm_start", C.c_int),
+        ("tol", C.c_double),
+        ("min_sweeps", C.c_int),
+    ]
+
+
 # every symbol declared in include/smpc.h
 SYMBOLS = [
     "smpc_builtin_robot", "smpc_last_error", "smpc_device_count", "smpc_create", "smpc_create_centroidal", "smpc_create_fulldynamics", "smpc_get_contact_forces", "smpc_destroy", "smpc_get_dims",
@@ -173,6 +181,8 @@ SYMBOLS = [
     "smpc_robot_sim_create", "smpc_robot_sim_destroy", "smpc_robot_sim_get_dims", "smpc_robot_sim_wait", "smpc_robot_sim_get_stream", "smpc_robot_sim_share_stream", "smpc_robot_sim_forward_dynamics", "smpc_robot_sim_step_device", "smpc_robot_sim_get_last", "smpc_robot_sim_read_last",
     "smpc_robot_sim_set_ground", "smpc_robot_sim_get_ground_dims", "smpc_robot_sim_step_ground_device", "smpc_robot_sim_ground_dynamics", "smpc_robot_sim_get_ground_last", "smpc_robot_sim_read_ground_last",
     "smpc_robot_sim_set_ground_env", "smpc_robot_sim_set_ground_push", "smpc_robot_sim_get_ground_push", "smpc_robot_sim_ground_env_dynamics",
+    "smpc_robot_sim_set_ground_solver", "smpc_robot_sim_reset_ground_warm_start", "smpc_robot_sim_reset_ground_warm_start_device", "smpc_robot_sim_get_ground_solver_last",
+    "smpc_robot_sim_read_ground_solver_last", "smpc_robot_sim_ground_solve_dynamics",
 ]
 
 
@@ -319,6 +329,13 @@ class SmpcLib:
         L.smpc_robot_sim_set_ground_push.argtypes = [vp, C.c_int, vp]
         L.smpc_robot_sim_get_ground_push.argtypes = [vp, C.POINTER(vp)]
         L.smpc_robot_sim_ground_env_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+        L.smpc_robot_sim_set_ground_solver.argtypes = [vp, C.POINTER(GroundSolverSettingsC)]
+        L.smpc_robot_sim_reset_ground_warm_start.argtypes = [vp, vp, C.c_int]
+        L.smpc_robot_sim_reset_ground_warm_start_device.argtypes = [vp, vp]
+        L.smpc_robot_sim_get_ground_solver_last.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.smpc_robot_sim_read_ground_solver_last.argtypes = [vp, vp, vp]
+        L.smpc_robot_sim_ground_solve_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, vp, vp, vp, C.c_int, C.POINTER(GroundSolverSettingsC), vp, vp, vp, vp, vp,
+                                                           vp, vp, vp, vp]
 
     def check(self, code):
         if code < 0:

@@ -27,7 +27,19 @@ The per-robot environment, same method:
 
 `run-env`: per robot of GROUND_RUNS, instantiation and sweep count stepGroundDevice on a handle without an environment (sim_ground_rt_body:
 the yardstick of the same run), then on the same handle after setGroundEnv / setPush with the uniform environment (sim_ground_env_rt_body:
-the same answers bit for bit).  `summary-env`: both columns, their ratio, the cost of a sweep and the intercept at zero sweeps of each."""
+the same answers bit for bit).  `summary-env`: both columns, their ratio, the cost of a sweep and the intercept at zero sweeps of each.
+
+The warm-started solve with a stopping rule, same method:
+
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -o ws -- python3 tools/sim_rt_profile.py run-ws [batch]
+    python3 tools/sim_rt_profile.py summary-ws <kernel_trace.csv> [batch]
+
+`run-ws`, per robot of WS_RUNS: (a) the cost of the bookkeeping -- at each of GROUND_SWEEPS sweeps stepGroundDevice after setGroundEnv / setPush
+with the uniform environment (sim_ground_env_rt_body: the yardstick of the same run), then on the same handle after setGroundSolver with
+warm_start = 0, tol = 0 (sim_ground_ws_rt_body: the same answers bit for bit); (b) what the feature buys -- robots at rest on the plane under
+small random torques, tol = 1e-6, sweeps = 60, once cold and once warm, with the distribution of sweeps_used printed at launches 1, 5 and 20
+after the warm-up.  `summary-ws`: (a) both columns, per-sweep cost and intercept of each; (b) launch µs cold and warm as the minimum of
+the readings, and at launches 1, 5 and 20."""
 import collections
 import csv
 import os
@@ -140,6 +152,107 @@ def run_env(B):
                       flush=True)
 
 
+WS_RUNS = [("go2_like", 3, 1), ("biped_legs", 6, 4)]  # (robot, contact size of the handle, points per foot): 4 points on <12>, 8 points on <24>
+WS_TOL, WS_SWEEPS, WS_SAMPLES = 1e-6, 60, (1, 5, 20)
+
+
+def run_ws(B):
+    sys.path[:0] = [os.path.join(ROOT, "simple-mpc_amd", "python"), os.path.join(ROOT, "tests")]
+    import numpy as np
+    import torch
+    import robot_tables as RT
+    import simple_mpc
+    import test_id_any_robot as T
+
+    for name, fs, P in WS_RUNS:
+        tab = T.table(name)
+        rb = RT.oracle_robot(tab)
+        sim = simple_mpc.BatchedRobotSim(RT.model_handler(tab), force_size=fs, batch=B)
+        gz = float(rb.centroidal(rb.x_ref)["feet"][:, 2].min())
+        X = RT.near_reference_states(rb, min(B, 64), seed=5, scale=0.3)
+        X = np.tile(X, (-(-B // X.shape[0]), 1))[:B]
+        td = torch.from_numpy(np.random.default_rng(6).normal(0.0, 1.0, (B, rb.nv - 6))).cuda()
+        # (a) the bookkeeping: inert settings against the kernel of the per-robot environment
+        for sw in GROUND_SWEEPS:
+            ends = []
+            for ws in (False, True):
+                sim.setGround(ground_z=gz, points=GROUND_POINTS[P], sweeps=sw)  # (drops the settings of the run before)
+                sim.setGroundEnv(planes=np.tile([0.0, 0.0, 1.0, gz], (B, 1)), mu=np.full(B, 0.7))
+                sim.setPush(np.zeros((B, 6)))
+                if ws:
+                    sim.setGroundSolver(warm_start=False, tol=0.0)
+                Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
+                torch.cuda.synchronize()
+                for _ in range(WARM + READINGS * LAUNCHES):
+                    sim.stepGroundDevice(Xd.data_ptr(), td.data_ptr(), 1e-3)
+                sim.wait()
+                ends.append(Xd.cpu().numpy())
+            print(name, "P", P, "sweeps", sw, "inert settings: finite:", bool(np.isfinite(ends[0]).all()), "the two kernels agree bit for bit:",
+                  bool(np.array_equal(ends[0], ends[1])), flush=True)
+        # (b) at rest on the plane, cold and warm
+        X0 = np.tile(rb.x_ref, (B, 1))
+        for warm in (False, True):
+            sim.setGround(ground_z=gz, points=GROUND_POINTS[P], sweeps=WS_SWEEPS)
+            sim.setGroundSolver(warm_start=warm, tol=WS_TOL)
+            Xd = torch.from_numpy(np.ascontiguousarray(X0)).cuda()
+            torch.cuda.synchronize()
+            for k in range(WARM + READINGS * LAUNCHES):
+                sim.stepGroundDevice(Xd.data_ptr(), td.data_ptr(), 1e-3)
+                if k + 1 - WARM in WS_SAMPLES:
+                    s = sim.lastGroundSweeps()  # (joins the stream)
+                    q = np.percentile(s, [0, 10, 50, 90, 100]).astype(int).tolist()
+                    print(name, "P", P, "warm" if warm else "cold", "launch", k + 1 - WARM, "sweeps_used min / 10 % / median / 90 % / max", q, "mean %.2f" % s.mean(),
+                          "largest residual %.2e" % np.nanmax(sim.lastGroundResiduals()), flush=True)
+            sim.wait()
+            print(name, "P", P, "warm" if warm else "cold", "finite:", bool(np.isfinite(Xd.cpu().numpy()).all()), flush=True)
+
+
+def summary_ws(trace, B):
+    d = []  # (kernel, duration) in launch order
+    for r in sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"])):
+        grid = int(r["Grid_Size"]) if "Grid_Size" in r else int(r["Grid_Size_X"])
+        m = re.search(r"(sim_ground_env_rt_body|sim_ground_ws_rt_body)(?:<|ILi)(\d+)", r["Kernel_Name"])
+        if m and grid == B * 64:
+            d.append(("%s<%s>" % m.groups(), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3))
+    per = WARM + READINGS * LAUNCHES
+    assert len(d) == per * len(WS_RUNS) * (2 * len(GROUND_SWEEPS) + 2), len(d)
+
+    def reading(blk):
+        t = [v for _, v in blk[WARM:]]
+        means = [sum(t[i * LAUNCHES: (i + 1) * LAUNCHES]) / LAUNCHES for i in range(READINGS)]
+        return min(means), 100 * (max(means) / min(means) - 1.0), t
+
+    print("| robot | rows | points | sweeps | `sim_ground_env_rt_body` µs (spread) | `sim_ground_ws_rt_body`, inert µs (spread) | ratio |")
+    print("|---|---|---|---|---|---|---|")
+    k, rest = 0, []
+    for name, fs, P in WS_RUNS:
+        cols = ([], [])
+        for sw in GROUND_SWEEPS:
+            cell = []
+            for ws in (0, 1):
+                blk = d[k * per: (k + 1) * per]
+                k += 1
+                assert len(set(n for n, _ in blk)) == 1 and ("ws" in blk[0][0]) == bool(ws), set(n for n, _ in blk)
+                t, sp, _ = reading(blk)
+                cols[ws].append(t)
+                cell.append("%.1f (%.1f %%)" % (t, sp))
+            print("| %s | %s | %d | %d | %s | %s | %.3f |" % (name, blk[0][0][-3:-1], P * T_NFEET[name], sw, cell[0], cell[1], cols[1][-1] / cols[0][-1]))
+        span = GROUND_SWEEPS[-1] - GROUND_SWEEPS[0]
+        slopes = [(c[-1] - c[0]) / span for c in cols]
+        print("| %s |  | %d | per sweep / intercept | %.2f / %.1f | %.2f / %.1f | |"
+              % (name, P * T_NFEET[name], slopes[0], cols[0][0] - GROUND_SWEEPS[0] * slopes[0], slopes[1], cols[1][0] - GROUND_SWEEPS[0] * slopes[1]))
+        for warm in (0, 1):
+            blk = d[k * per: (k + 1) * per]
+            k += 1
+            assert len(set(n for n, _ in blk)) == 1 and "ws" in blk[0][0], set(n for n, _ in blk)
+            rest.append((name, P * T_NFEET[name], "warm" if warm else "cold") + reading(blk))
+    print()
+    print("| robot | points | start | launch µs, minimum of the readings (spread) | at launch %s |" % " / ".join(str(s) for s in WS_SAMPLES))
+    print("|---|---|---|---|---|")
+    for name, pts, start, t, sp, all_t in rest:
+        print("| %s | %d | %s | %.1f (%.1f %%) | %s |" % (name, pts, start, t, sp, " / ".join("%.1f" % all_t[s - 1] for s in WS_SAMPLES)))
+
+
 def summary_env(trace, B):
     d = []  # (kernel, duration) in launch order
     for r in sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"])):
@@ -241,6 +354,10 @@ if __name__ == "__main__":
         run_ground(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     elif sys.argv[1] == "run-env":
         run_env(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+    elif sys.argv[1] == "run-ws":
+        run_ws(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
+    elif sys.argv[1] == "summary-ws":
+        summary_ws(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 4096)
     elif sys.argv[1] == "summary-env":
         summary_env(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 4096)
     elif sys.argv[1] == "summary-ground":
