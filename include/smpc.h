@@ -319,13 +319,22 @@ int smpc_get_status(smpc_handle * h, int * out);
 int smpc_get_cold_trace(smpc_handle * h, double * out, int cap);
 
 /* test / debug access to one LQ knot (stage t of instance inst) as assembled by the stage kernel in the
- * LAST iteration: out must hold smpc_lq_size() doubles, laid out A,B,Q,S,R,C,q,r,f,d,lx,lu,lpd,vpd */
+ * LAST iteration: out must hold smpc_lq_size() doubles, laid out A,B,Q,S,R,C,q,r,f,d,lx,lu,lpd,vpd.
+ * Centroidal handles answer too (row-major, vector conventions of the oracle's Knot):
+ *   point feet: A 9x9, B 9xnu, Q 9x9, S 9xnu, R nuxnu, Dd ncxnu (cone rows; Cd is structurally zero; an inactive row is zero), q 9, r nu, f 9,
+ *               d nc, act nc (1.0 / 0.0), any ("a cone row of the stage is active"), preg (the regularisation the iteration used) --
+ *               the stage record of the kernel pipeline, unpacked on the host through the maps the backward sweep gathers through;
+ *   6-D feet:   the dense knot of the sweep: the full-dynamics layout A,B,Q,S,R,Cd,Dd,q,r,f,d,lx,lu,lpd,vpd,act,cdirty with ndx = 12 (the state
+ *               padded from 9 to 12) and nu + 17 nfeet rows (the nu control-box rows are absent);
+ *   a handle created with SMPC_CENT_FUSED=1 (cross-check build) keeps no record and answers SMPC_ERR_INVALID. */
 int smpc_lq_size(const smpc_handle * h);
 int smpc_debug_get_lq(smpc_handle * h, int inst, int t, double * out);
 /* last line-search steps: dxs [B][H+1][ndx], dus [B][H][nu] */
 int smpc_debug_get_steps(smpc_handle * h, double * dxs, double * dus);
-/* terminal node of the last iteration for one instance: QN [ndx][ndx], qN [ndx] */
+/* terminal node of the last iteration for one instance: QN [ndx][ndx], qN [ndx] (centroidal handles with 6-D feet: ndx = 12, as their knot) */
 int smpc_debug_get_terminal(smpc_handle * h, int inst, double * QN, double * qN);
+/* last multiplier steps of a centroidal handle: dvs [B][H][nc], dlams [B][H][9] with dlams[t] = step of lambda_{t+1} */
+int smpc_debug_get_dual_steps(smpc_handle * h, double * dvs, double * dlams);
 
 /* in-kernel phase timers of the Riccati sweep (shader cycles, block 0 only); needs SMPC_PHASE_PROFILE=1
  * in the environment at smpc_create time. out: 64 doubles */

@@ -114,7 +114,7 @@ namespace
       }
     }
   }
-  // LQ knot (b, t) of the last iteration, packed A,B,Q,S,R,C,q,r,f,d (row-major)
+  // LQ knot (b, t) of the last iteration, packed A,B,Q,S,R,C,q,r,f,d,D (row-major; D last: the offsets of the fields before it are those of old)
   template <class MPC>
   int mpc_get_knot_impl(MPC * m, int b, int t, double * out)
   {
@@ -132,6 +132,8 @@ namespace
       vec_to(*v, o);
       o += v->size();
     }
+    mat_to(k.D, o);
+    o += k.D.a.size();
     return (int)(o - out);
   }
   // ProxDDP on an H-stage problem with per-stage references, run to convergence with the stopping rules of the cold solve (orc_mpc.hpp) --
@@ -1125,6 +1127,17 @@ extern "C"
     m->last_knots.assign(m->B, std::vector<Knot>());
   }
   int orc_cmpc_get_knot(void * h, int b, int t, double * out) { return mpc_get_knot_impl((BatchMPCCent *)h, b, t, out); }
+  // terminal node (QN [ndx][ndx], qN [ndx]) and primal regularisation of the last iteration of instance b (after keep_knots)
+  int orc_cmpc_get_terminal(void * h, int b, double * QN, double * qN, double * preg)
+  {
+    BatchMPCCent * m = (BatchMPCCent *)h;
+    if (b < 0 || b >= (int)m->last_term.size() || m->last_term[b].QN.a.empty())
+      return -1;
+    mat_to(m->last_term[b].QN, QN);
+    vec_to(m->last_term[b].qN, qN);
+    *preg = m->last_term[b].preg;
+    return 0;
+  }
   int orc_cmpc_cold_iters(void * h) { return (int)((BatchMPCCent *)h)->cold_trace.size(); }
   void orc_cmpc_cold_trace(void * h, double * out)
   {

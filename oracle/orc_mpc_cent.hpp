@@ -39,6 +39,7 @@ namespace orc
     std::vector<IterInfo> cold_trace;
     bool keep_knots = false;
     std::vector<std::vector<Knot>> last_knots;
+    std::vector<TermKnot> last_term; // [b], filled when keep_knots (tests only)
 
     static Vec centroidal_state(Rigid & R, const smpc_robot_model * m, const double * x)
     {
@@ -195,7 +196,10 @@ namespace orc
         horizon[H - 1].x_tgt[6 + i] = md.mass * velocity_base[3 + i];
       }
       if (keep_knots)
+      {
         last_knots.resize(B);
+        last_term.resize(B);
+      }
 
       ProxDDPT<CentModel> solver(md, st.mu_init);
 #pragma omp parallel for schedule(dynamic)
@@ -269,7 +273,7 @@ namespace orc
         std::vector<Vec> vs_e = S.vs, lams_e = S.lams;
         S.preg = SolverConsts::REG_INIT;
         for (int it = 0; it < st.max_iters; it++)
-          last_info[b] = solver.iterate(R, o, S, vs_e, lams_e, keep_knots ? &last_knots[b] : nullptr);
+          last_info[b] = solver.iterate(R, o, S, vs_e, lams_e, keep_knots ? &last_knots[b] : nullptr, nullptr, -1.0, keep_knots ? &last_term[b] : nullptr);
       }
     }
   };

@@ -36,6 +36,13 @@ namespace orc
     Mat Q, S, R, A, B, C, D;
     Vec q, r, f, d;
   };
+  // terminal node of an iteration as the Riccati recursion starts from it, and the primal regularisation the iteration's knots carry
+  struct TermKnot
+  {
+    Mat QN;
+    Vec qN;
+    double preg = 0.0;
+  };
   struct Gains
   {
     Mat K, Z, Pt; // K (nu x ndx), Z (nc x ndx), Pt = P~_{t+1} (ndx x ndx)
@@ -365,7 +372,8 @@ namespace orc
     // One full iteration; vs_e / lams_e are the AL centres.
     IterInfo iterate(
       Rigid & R, const OcpInstance & ocp, SolverState & S, const std::vector<Vec> & vs_e,
-      const std::vector<Vec> & lams_e, std::vector<Knot> * knots_out = nullptr, const Vec * vN_e = nullptr, double stop_tol = -1.0) const
+      const std::vector<Vec> & lams_e, std::vector<Knot> * knots_out = nullptr, const Vec * vN_e = nullptr, double stop_tol = -1.0,
+      TermKnot * term_out = nullptr) const
     {
       const int H = (int)ocp.stages.size();
       const int ndx = md.ndx, nu = md.nu, nc = md.nc;
@@ -462,6 +470,12 @@ namespace orc
       }
       if (knots_out)
         *knots_out = kn;
+      if (term_out)
+      {
+        term_out->QN = QN;
+        term_out->qN = qN;
+        term_out->preg = S.preg;
+      }
 
       std::vector<Vec> dxs, dus, dvs, dlams;
       prox_riccati(kn, QN, qN, mu, dxs, dus, dvs, dlams, &S.Ks);

@@ -740,8 +740,8 @@ extern "C"
         out[i * 4 + k] = h->e->cold_trace[(size_t)i * 4 + k];
     return n;
   }
-  // (size of what smpc_debug_get_lq returns.  A handle without knots of its own -- centroidal, null -- reports the row-major form of a
-  // Go2 kinodynamics knot, as this entry point always has.)
+  // (size of what smpc_debug_get_lq returns.  A null handle reports the row-major form of a Go2 kinodynamics knot, as this entry point
+  // always has.)
   int smpc_lq_size(const smpc_handle * h)
   {
     const int n = h ? h->e->lq_size() : 0;
@@ -770,6 +770,12 @@ extern "C"
     if (!h || !QN || !qN)
       return fail(SMPC_ERR_INVALID, "null argument");
     return guarded([&] { h->e->debug_terminal(inst, QN, qN); });
+  }
+  int smpc_debug_get_dual_steps(smpc_handle * h, double * dvs, double * dlams)
+  {
+    if (!h || !dvs || !dlams)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    return guarded([&] { h->e->debug_dual_steps(dvs, dlams); });
   }
   int smpc_debug_get_phase_cycles(smpc_handle * h, double * out64)
   {

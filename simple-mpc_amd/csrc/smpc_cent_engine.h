@@ -903,10 +903,147 @@ namespace smpc
     {
       throw InvalidCall("smpc_set_early_exit_on_tol: kinodynamics and full-dynamics handles (the centroidal step is one fused kernel)");
     }
+    // the kernel pipeline of point feet keeps its steps on the iterate's ring slots [B][R][.] (smpc_cent_split.h); the 6-D path and the
+    // one-kernel form keep them linear in t
+    bool steps_on_ring() const { return DC::FS == 3 && !fused; }
     void debug_steps(double * dxs, double * dus) override
     {
+      if (steps_on_ring())
+      {
+        get_ring(buf.dxs, 9, H + 1, dxs);
+        get_ring(buf.dus, DC::NU, H, dus);
+        return;
+      }
       get_linear(buf.dxs, (size_t)B * (H + 1) * 9, dxs);
       get_linear(buf.dus, (size_t)B * H * DC::NU, dus);
+    }
+    // smpc_debug_get_dual_steps: dvs [B][H][nc], dlams [B][H][9] with dlams[t] = dlambda_{t+1}
+    void debug_dual_steps(double * dvs, double * dlams) override
+    {
+      if (steps_on_ring())
+      {
+        get_ring(buf.dvs, DC::NC, H, dvs);
+        get_ring(buf.dlams, 9, H, dlams);
+        return;
+      }
+      get_linear(buf.dvs, (size_t)B * H * DC::NC, dvs);
+      get_linear(buf.dlams, (size_t)B * H * 9, dlams);
+    }
+    // ---- the LQ knot the sweeps of the last iteration solved (debug surface; TEST INFRASTRUCTURE of tests/sweep_check.py) ----
+    // point feet: the record of stage (inst, t), unpacked through CentRec's own maps (the maps cent_bwd_body gathers through) into
+    //   A 9x9 | B 9xNU | Q 9x9 | S 9xNU | R NUxNU | Dd NCxNU | q 9 | r NU | f 9 | d NC | act NC | any | preg
+    // in the vector conventions of the oracle's Knot (Cd is structurally zero; a cone row is active when its Jacobian row is in the record).
+    // 6-D feet: the dense knot of the sweep, layout DC::DD (state padded to 12).
+    static constexpr int KN_A = 0, KN_B = KN_A + 81, KN_Q = KN_B + 9 * DC::NU, KN_S = KN_Q + 81, KN_R = KN_S + 9 * DC::NU, KN_D = KN_R + DC::NU * DC::NU,
+                         KN_q = KN_D + DC::NC * DC::NU, KN_r = KN_q + 9, KN_f = KN_r + DC::NU, KN_d = KN_f + 9, KN_act = KN_d + DC::NC, KN_any = KN_act + DC::NC,
+                         KN_preg = KN_any + 1, KN_N = KN_preg + 1;
+    int lq_size() const override
+    {
+      if constexpr (DC::FS == 6)
+        return DC::DD::LQ_STRIDE;
+      else
+        return KN_N;
+    }
+    void check_knot_source() const
+    {
+      if (fused)
+        throw InvalidCall("a centroidal handle created with SMPC_CENT_FUSED=1 runs the one-kernel control step, which keeps no stage record: no knot to return");
+    }
+    void debug_lq(int inst, int t, double * out) override
+    {
+      check_knot_source();
+      if (inst < 0 || inst >= B || t < 0 || t >= H)
+        throw InvalidCall("Stage index exceeds stage vector size");
+      if constexpr (DC::FS == 6)
+      {
+        typedef typename DC::DD DD;
+        get_linear(x6.sb.lq + ((size_t)inst * H + t) * DD::LQ_STRIDE, DD::LQ_STRIDE, out);
+        // (upper triangles of Q and R are what the derivative pass writes and the sweep reads: mirror, as FullEngine::debug_lq)
+        for (int i = 0; i < DD::NDX; i++)
+          for (int j = 0; j < i; j++)
+            out[DD::O_Q + i * DD::NDX + j] = out[DD::O_Q + j * DD::NDX + i];
+        for (int i = 0; i < DD::NU; i++)
+          for (int j = 0; j < i; j++)
+            out[DD::O_R + i * DD::NU + j] = out[DD::O_R + j * DD::NU + i];
+      }
+      else
+      {
+        typedef CentRec<DC> RC;
+        constexpr int NU = DC::NU, NC = DC::NC;
+        std::vector<double> stg(RC::STAGE_N, 0.0), sc(SC_N);
+        get_linear(sbuf.rec + ((size_t)inst * H + t) * RC::STRIDE, RC::STRIDE, stg.data());
+        get_linear(buf.scal + (size_t)inst * SC_N, SC_N, sc.data());
+        CentDevModel<DC> mg;
+        static_assert(sizeof(CentDevModel<DC>) % sizeof(double) == 0, "the device model is an array of doubles");
+        get_linear(reinterpret_cast<const double *>(buf.model), sizeof(mg) / sizeof(double), reinterpret_cast<double *>(&mg));
+        // the constants cent_bwd_body keeps behind the record in LDS; preg: the value the last iteration used, parked by the line search
+        const double preg = sc[SC_PREG_OLD];
+        stg[RC::C_ONE] = 1.0;
+        stg[RC::C_DTM] = mg.dt / mg.mass;
+        stg[RC::C_NMU] = -mg.mu;
+        for (int a = 0, e = 0; a < 3; a++)
+          for (int bb = a; bb < 3; bb++, e++)
+          {
+            stg[RC::C_QLM + e] = mg.w_lm[a * 3 + bb] + (a == bb ? preg : 0.0);
+            stg[RC::C_QAM + e] = mg.w_am[a * 3 + bb] + (a == bb ? preg : 0.0);
+          }
+        const double * s = stg.data();
+        for (int k = 0; k < 9; k++)
+        {
+          for (int i = 0; i < 9; i++)
+          {
+            out[KN_A + k * 9 + i] = s[RC::ab_off(k, RC::XO + i)];
+            out[KN_Q + k * 9 + i] = s[RC::m2_off(RC::XO + k, RC::XO + i)];
+          }
+          for (int j = 0; j < NU; j++)
+          {
+            out[KN_B + k * NU + j] = s[RC::ab_off(k, j)];
+            out[KN_S + k * NU + j] = s[RC::m2_off(j, RC::XO + k)];
+          }
+          out[KN_q + k] = s[RC::m2_off(RC::XO + k, RC::ZC)];
+          out[KN_f + k] = s[RC::O_F + k];
+        }
+        for (int i = 0; i < NU; i++)
+        {
+          for (int j = 0; j < NU; j++)
+            out[KN_R + i * NU + j] = s[RC::m2_off(i, j)];
+          out[KN_r + i] = s[RC::m2_off(i, RC::ZC)];
+        }
+        for (int row = 0; row < NC; row++)
+        {
+          bool act = false;
+          for (int j = 0; j < NU; j++)
+          {
+            const double v = s[RC::m2_off(j, RC::cone_slot(row))];
+            out[KN_D + row * NU + j] = v;
+            act = act || v != 0.0;
+          }
+          out[KN_d + row] = s[RC::m2_off(RC::cone_slot(row), RC::ZC)];
+          out[KN_act + row] = act ? 1.0 : 0.0;
+        }
+        out[KN_any] = s[RC::O_ANY];
+        out[KN_preg] = preg;
+      }
+    }
+    void debug_terminal(int inst, double * QN, double * qN) override
+    {
+      check_knot_source();
+      if (inst < 0 || inst >= B)
+        throw InvalidCall("instance index out of range");
+      if constexpr (DC::FS == 6)
+      {
+        typedef typename DC::DD DD;
+        get_linear(x6.sb.QN + (size_t)inst * DD::NDX * DD::NDX, DD::NDX * DD::NDX, QN);
+        get_linear(x6.sb.qN + (size_t)inst * DD::NDX, DD::NDX, qN);
+      }
+      else
+      {
+        typedef CentRec<DC> RC;
+        std::vector<double> tr(RC::T_STRIDE);
+        get_linear(sbuf.term + (size_t)inst * RC::T_STRIDE, RC::T_STRIDE, tr.data());
+        std::copy(tr.begin() + RC::T_P, tr.begin() + RC::T_P + 81, QN);
+        std::copy(tr.begin() + RC::T_p, tr.begin() + RC::T_p + 9, qN);
+      }
     }
     void phase_cycles(double * out64) override
     {

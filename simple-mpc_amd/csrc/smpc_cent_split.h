@@ -1418,6 +1418,7 @@ namespace smpc
         s.sc[SC_LS_FAILED] = accepted < 0 ? 1.0 : 0.0;
         s.sc[SC_LS_INDEX] = (double)jlast;
         s.sc[SC_PREG] = accepted < 0 ? fmin(preg * ka.reg_inc, ka.reg_max) : fmax(preg * ka.reg_dec, ka.reg_min);
+        s.sc[SC_PREG_OLD] = preg; // (the regularisation this iteration's knots were built with: CentEngine::debug_lq)
       }
     }
     SMPC_LANES_END_WAVE
@@ -1744,6 +1745,7 @@ namespace smpc
         s.sc[SC_LS_FAILED] = accepted < 0 ? 1.0 : 0.0;
         s.sc[SC_LS_INDEX] = (double)jlast;
         s.sc[SC_PREG] = accepted < 0 ? fmin(preg * ka.reg_inc, ka.reg_max) : fmax(preg * ka.reg_dec, ka.reg_min);
+        s.sc[SC_PREG_OLD] = preg; // (the regularisation this iteration's knots were built with: CentEngine::debug_lq)
       }
     }
     SMPC_LANES_END_WAVE

@@ -553,6 +553,7 @@ namespace smpc
     virtual int lq_size() const { return 0; } // doubles of what debug_lq returns (0: no knots to return)
     virtual void debug_lq(int, int, double *) { throw InvalidCall(KINO_ONLY); }
     virtual void debug_terminal(int, double *, double *) { throw InvalidCall(KINO_ONLY); }
+    virtual void debug_dual_steps(double *, double *) { throw InvalidCall("smpc_debug_get_dual_steps needs a centroidal handle (smpc_create_centroidal)"); }
     virtual void phase_cycles(double * out64) = 0;
     virtual void debug_frontend_rt(const double *, double *, double *, double *, double *)
     {

@@ -1121,10 +1121,43 @@ class BatchedMPC:
                 ("Dd", (ncone, nu)), ("Cv", (nvel, ndx)), ("q", (ndx,)), ("r", (nu,)), ("f", (ndx,)), ("d", (nc,)), ("lx", (ndx,)),
                 ("lu", (nu,)), ("lpd", (ndx,)), ("vpd", (nc,)), ("act", (nc,)), ("cdirty", ()),
             )
+        cent6 = False
+        if isinstance(self.ocp_handler, CentroidalOCP):
+            if int(self.ocp_handler.settings.get("force_size", 3)) == 6:
+                # dense knot of the 6-D centroidal sweep (smpc_cent6_kernels.h, Cent6Dims): the state padded from 9 to 12, rows [control box
+                # (absent: flags stay 0) | 17 wrench-cone rows per foot]; returned cut to the nine real state rows / columns, the padding under
+                # "pad" (A, Q: the three pad rows and columns; B, S, Cd: the pad rows / columns; q, f: the pad entries)
+                cent6, ndx, nc = True, 12, nu + nc
+                layout = (
+                    ("A", (ndx, ndx)), ("B", (ndx, nu)), ("Q", (ndx, ndx)), ("S", (ndx, nu)), ("R", (nu, nu)), ("Cd", (nc - nu, ndx)),
+                    ("Dd", (nc - nu, nu)), ("q", (ndx,)), ("r", (nu,)), ("f", (ndx,)), ("d", (nc,)), ("lx", (ndx,)), ("lu", (nu,)),
+                    ("lpd", (ndx,)), ("vpd", (nc,)), ("act", (nc,)), ("cdirty", ()),
+                )
+            else:
+                # stage record of the point-foot pipeline, unpacked by the library (include/smpc.h): Cd is structurally zero
+                layout = (
+                    ("A", (ndx, ndx)), ("B", (ndx, nu)), ("Q", (ndx, ndx)), ("S", (ndx, nu)), ("R", (nu, nu)), ("Dd", (nc, nu)), ("q", (ndx,)),
+                    ("r", (nu,)), ("f", (ndx,)), ("d", (nc,)), ("act", (nc,)), ("any", ()), ("preg", ()),
+                )
         for name, shape in layout:
             sz = int(np.prod(shape))
             res[name] = out[o : o + sz].reshape(shape).copy()
             o += sz
+        if cent6:
+            n = self.ndx
+            res["pad"] = dict(
+                A_rows=res["A"][n:, :], A_cols=res["A"][:, n:], Q_rows=res["Q"][n:, :], Q_cols=res["Q"][:, n:], B=res["B"][n:, :],
+                S=res["S"][n:, :], Cd=res["Cd"][:, n:], q=res["q"][n:], f=res["f"][n:], lx=res["lx"][n:], lpd=res["lpd"][n:],
+            )
+            for k in ("A", "Q"):
+                res[k] = res[k][:n, :n].copy()
+            for k in ("B", "S", "q", "f", "lx", "lpd"):
+                res[k] = res[k][:n].copy()
+            res["Cd"] = res["Cd"][:, :n].copy()
+            # (the control-box rows are absent: d, vpd, act of the nc wrench-cone rows)
+            for k in ("d", "vpd", "act"):
+                assert not res[k][:nu].any(), "control-box rows of the 6-D centroidal knot must stay empty"
+                res[k] = res[k][nu:].copy()
         return res
 
     def debug_steps(self):
@@ -1133,9 +1166,22 @@ class BatchedMPC:
         self._lib.check(self._lib.L.smpc_debug_get_steps(self._h, dxs, dus))
         return dxs, dus
 
-    def debug_terminal(self, inst):
-        QN, qN = np.zeros((self.ndx, self.ndx)), np.zeros(self.ndx)
+    def debug_dual_steps(self):
+        """Multiplier steps of the last iteration (centroidal handles): dvs [B][H][nc], dlams [B][H + 1][ndx] with dlams[:, 0] = 0 (the
+        library returns the steps of lambda_1 .. lambda_H)."""
+        dvs = np.zeros((self.B, self.H, self.nc))
+        dl = np.zeros((self.B, self.H, self.ndx))
+        self._lib.check(self._lib.L.smpc_debug_get_dual_steps(self._h, dvs, dl))
+        return dvs, np.concatenate([np.zeros((self.B, 1, self.ndx)), dl], axis=1)
+
+    def debug_terminal(self, inst, padded=False):
+        n = self.ndx
+        if isinstance(self.ocp_handler, CentroidalOCP) and int(self.ocp_handler.settings.get("force_size", 3)) == 6:
+            n = 12  # (the padded state of the dense sweep; cut to the real block unless `padded`)
+        QN, qN = np.zeros((n, n)), np.zeros(n)
         self._lib.check(self._lib.L.smpc_debug_get_terminal(self._h, inst, QN, qN))
+        if n != self.ndx and not padded:
+            return QN[: self.ndx, : self.ndx].copy(), qN[: self.ndx].copy()
         return QN, qN
 
     def set_profiling(self, on):

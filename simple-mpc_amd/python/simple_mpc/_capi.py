@@ -175,7 +175,7 @@ SYMBOLS = [
     "smpc_get_vs", "smpc_get_lams", "smpc_get_state_derivative01", "smpc_set_retain_state_derivatives", "smpc_get_state_derivatives",
     "smpc_get_state_derivatives_device", "smpc_get_reference_poses",
     "smpc_set_early_exit_on_tol", "smpc_iterate_async", "smpc_gather_outputs", "smpc_gather_outputs_device", "smpc_gather_outputs_peer", "smpc_get_foot_timing", "smpc_get_info", "smpc_get_status", "smpc_get_cold_trace", "smpc_lq_size", "smpc_debug_get_lq",
-    "smpc_debug_get_steps", "smpc_debug_get_terminal", "smpc_debug_get_phase_cycles", "smpc_set_profiling", "smpc_get_kernel_times", "smpc_get_kernel_times_n", "smpc_kernel_time_slots", "smpc_reset_kernel_times",
+    "smpc_debug_get_steps", "smpc_debug_get_terminal", "smpc_debug_get_dual_steps", "smpc_debug_get_phase_cycles", "smpc_set_profiling", "smpc_get_kernel_times", "smpc_get_kernel_times_n", "smpc_kernel_time_slots", "smpc_reset_kernel_times",
     "smpc_interpolate", "smpc_interpolate_knots", "smpc_friction_compensation", "smpc_update_internal_data", "smpc_debug_frontend_rt", "smpc_full_forward_dynamics", "smpc_centroidal_dynamics", "smpc_riccati_feedback",
     "smpc_id_create", "smpc_id_create_any", "smpc_id_destroy", "smpc_id_set_target", "smpc_id_set_targets", "smpc_id_set_target_centroidal", "smpc_id_set_targets_centroidal", "smpc_id_solve", "smpc_id_solve_device", "smpc_id_wait", "smpc_id_get_resid", "smpc_id_reset", "smpc_id_get_tau_device", "smpc_id_get_x_device", "smpc_id_set_targets_from_mpc", "smpc_id_share_stream", "smpc_sim_step_device", "smpc_id_debug_get", "smpc_id_get_dims", "smpc_debug_id_force_rt",
     "smpc_robot_sim_create", "smpc_robot_sim_destroy", "smpc_robot_sim_get_dims", "smpc_robot_sim_wait", "smpc_robot_sim_get_stream", "smpc_robot_sim_share_stream", "smpc_robot_sim_forward_dynamics", "smpc_robot_sim_step_device", "smpc_robot_sim_get_last", "smpc_robot_sim_read_last",
@@ -292,6 +292,7 @@ class SmpcLib:
         L.smpc_debug_get_lq.argtypes = [vp, C.c_int, C.c_int, _dp]
         L.smpc_debug_get_steps.argtypes = [vp, _dp, _dp]
         L.smpc_debug_get_terminal.argtypes = [vp, C.c_int, _dp, _dp]
+        L.smpc_debug_get_dual_steps.argtypes = [vp, _dp, _dp]
         L.smpc_debug_get_phase_cycles.argtypes = [vp, _dp]
         L.smpc_set_profiling.argtypes = [vp, C.c_int]
         L.smpc_get_kernel_times.argtypes = [vp, _dp, _lp]

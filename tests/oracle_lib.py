@@ -187,6 +187,7 @@ def lib():
     L.orc_cmpc_timing.argtypes = [vp, C.c_int, C.c_int, _ip, C.c_int]
     L.orc_cmpc_keep_knots.argtypes = [vp, C.c_int]
     L.orc_cmpc_get_knot.argtypes = [vp, C.c_int, C.c_int, _dp]
+    L.orc_cmpc_get_terminal.argtypes = [vp, C.c_int, _dp, _dp, _dp]
     L.orc_mpc_keep_knots.argtypes = [vp, C.c_int]
     L.orc_mpc_get_knot.argtypes = [vp, C.c_int, C.c_int, _dp]
     L.orc_centroidal_dynamics.argtypes = [C.c_double, _dp, C.c_double, C.c_int, _dp, _dp, _bp, _dp, _dp, _dp, _dp]
@@ -663,13 +664,13 @@ class OracleMPC:
     def knot(self, b, t):
         k = self.kino
         ndx, nu, nc = k.ndx, k.nu, k.nc
-        out = np.zeros(2 * ndx * ndx + 2 * ndx * nu + nu * nu + nc * ndx + 2 * ndx + nu + nc)
+        out = np.zeros(2 * ndx * ndx + 2 * ndx * nu + nu * nu + nc * ndx + 2 * ndx + nu + nc + nc * nu)
         n = self._f("get_knot")(self.h, b, t, out)
         assert n == out.size, n
         res, o = {}, 0
         for name, shape in (
             ("A", (ndx, ndx)), ("B", (ndx, nu)), ("Q", (ndx, ndx)), ("S", (ndx, nu)), ("R", (nu, nu)), ("C", (nc, ndx)),
-            ("q", (ndx,)), ("r", (nu,)), ("f", (ndx,)), ("d", (nc,)),
+            ("q", (ndx,)), ("r", (nu,)), ("f", (ndx,)), ("d", (nc,)), ("D", (nc, nu)),
         ):
             sz = int(np.prod(shape))
             res[name] = out[o : o + sz].reshape(shape).copy()
@@ -790,6 +791,14 @@ class OracleCentMPC(OracleMPC):
     @property
     def xdot(self):
         return self._get(7, (self.B, self.H, 18))[:, :, :9]
+
+    def terminal_knot(self, b):
+        """(QN, qN, preg) of the last iteration of instance b: the terminal node the Riccati recursion started from and the primal
+        regularisation the iteration's knots carry (after keep_knots())."""
+        n = self.kino.ndx
+        QN, qN, preg = np.zeros((n, n)), np.zeros(n), np.zeros(1)
+        assert lib().orc_cmpc_get_terminal(self.h, b, QN, qN, preg) == 0
+        return QN, qN, float(preg[0])
 
 
 class OracleFullMPC(OracleMPC):

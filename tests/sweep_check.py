@@ -22,7 +22,13 @@ Engine kinds
   * Talos kinodynamics (FullDims<..., KIN = 1>): as full dynamics; the frame-velocity rows Cv are already folded into Q / q by the stage
     kernel, so they do not enter C.  `lq_inputs(..., unfold_vel=True)` takes Cv^T Cv / mu and Cv^T d / mu out of Q / q again and hands the
     rows to the reference explicitly; `check_vel_fold` asserts that both forms give the same step (both sides on the CPU).
-  * centroidal handles have no knot accessor (debug_lq answers KINO_ONLY): out of scope.
+  * Go2 centroidal with point feet (the kernel pipeline of smpc_cent_split.h: cent_bwd_body, cent_fwd_body): debug_lq unpacks the stage record
+    through CentRec's own maps; C = 0, D = the cone rows Dd (an inactive row is a zero row).  The momentum blocks of Q are not in the record:
+    the accessor rebuilds them as the backward sweep does, w_lm | w_am + preg I, with the preg the line search parked.
+  * Talos centroidal with 6-D feet (cent6_deriv_body -> riccati_dense_body<DD> -> cent6_forward_body): the dense knot cut to the nine real
+    state rows and columns (the three pad rows / columns are exactly zero and decoupled: tests/test_centroidal_knots.py), C = Cd, D = Dd.
+  For both centroidal kinds `check` also compares the multiplier steps dvs and dlams of all stages with oracle_lib.riccati's ([Z z] has no
+  other read-out), and checks Ks at EVERY stage with `kkt_gain` (ndx = 9: cheap).
 
 Tolerances are measured, not chosen.  FLOOR is the largest per-stage gap between the two CPU references on the device's knots (emulated
 kernel bodies, measured at the parent of the commit that added this file, c443493) -- what two correct FP64 solvers disagree by at
@@ -43,7 +49,17 @@ Observed on the emulated bodies at that commit, as multiples of the floor: Go2 k
 engines <= 1.8, Talos kinodynamics 0.01 - 0.2.  On an MI355X (same commit, -m gpu): Go2 kinodynamics dxs 0.4 - 3.6,
 dus 0.3 - 4.8, Ks 1.5 - 4.4; dense engines <= 2.2; Talos kinodynamics 0.01 - 0.2; residual of the rebuilt rows over |dx+| 6e-16 .. 2e-14.
 
-FLOORS / GATES (per scenario; dxs, dus, Ks)
+Centroidal scenarios (floors measured on the emulated bodies at the commit that added them; absolute device gaps 1e-15 .. 2e-13 throughout, the
+floors themselves 1e-15 .. 4e-10, so most gates sit at the 1e-11 minimum).  Observed as multiples of the floor, emulated bodies: point feet
+dxs 0.001 - 1.3, dus 0.0001 - 0.97, Ks 0.014 - 0.85, dvs <= 0.41, dlams 0.014 - 1.8; 6-D feet <= 0.26.  On an MI355X (-m gpu): point feet dxs
+0.002 - 1.3, dus 0.0004 - 2.1, Ks 0.04 - 0.75, dvs 0.04 - 0.64, dlams 0.04 - 1.8 (the figures above 1 belong to cent_h2 and
+cent_cones_backtrack, whose floors are 1e-15 .. 1e-13); 6-D feet <= 0.13 except dvs of talos_cent_tight, 2.4 (2.3e-7 against a gate of 9.3e-7).
+talos_cent_tight dvs: dnu = (C dx + D du + d) / mu with mu = 1e-8 is a cancelling sum divided by mu, so both references (floor 9.3e-8 on the
+emulated knots, 1.3e-8 on the device's) and the device carry eps |D du| / (mu |dnu|); the rule stands as it is and every run prints the
+observed gap next to the gate.  cent_two_parts runs B = 128 as two parts of 64 (SMPC_CENT_PARTS=2: the engine splits by itself only from
+B = 1024 on) and checks the instances 0, 63, 64, 127.
+
+FLOORS / GATES (per scenario; dxs, dus, Ks -- centroidal scenarios: dxs, dus, Ks, dvs, dlams)
 %(table)s
 """
 import numpy as np
@@ -53,7 +69,7 @@ import scipy.sparse.linalg as spla
 
 import oracle_lib as O
 
-# scenario -> (floor dxs, floor dus, floor Ks): see the module docstring.  Filled from tools of this file: `floors(gm)` prints a row.
+# scenario -> (floor dxs, floor dus, floor Ks[, floor dvs, floor dlams]): see the module docstring.  Filled from tools of this file: `floors(gm)` prints a row.
 FLOORS = {
     "kino_record_k1": (9.2e-9, 3.2e-8, 6.8e-9),
     "kino_record_k1_dense": (9.2e-9, 3.2e-8, 6.8e-9),  # (the same knots to rounding: the floor of kino_record_k1)
@@ -69,16 +85,29 @@ FLOORS = {
     "talos_tight": (3.0e-13, 3.5e-13, 2.7e-13),
     "talos_kino_cone": (1.3e-7, 1.4e-6, 1.3e-8),
     "talos_walk_h100": (2.0e-12, 1.2e-12, 8.2e-13),
+    # centroidal: (dxs, dus, Ks at every stage, dvs, dlams), SC.floors on the emulated bodies (the largest of the checked control steps)
+    "cent_record_k1": (2.4e-12, 3.8e-12, 5.5e-13, 1.0e-13, 1.4e-13),
+    "cent_record_k3": (4.2e-12, 1.5e-10, 2.7e-13, 3.1e-13, 3.3e-13),
+    "cent_cones_backtrack": (7.2e-14, 3.9e-13, 8.4e-14, 5.4e-13, 1.3e-13),
+    "cent_h2": (1.3e-15, 5.0e-15, 4.9e-15, 0.0, 3.2e-15),
+    "cent_h63": (4.8e-12, 1.8e-11, 4.6e-14, 0.0, 1.1e-12),
+    "cent_h65": (1.4e-12, 2.1e-11, 4.3e-14, 0.0, 6.1e-14),
+    "cent_dense_w": (3.2e-13, 7.4e-13, 1.4e-14, 0.0, 3.6e-13),
+    "cent_two_parts": (5.2e-14, 1.5e-13, 9.5e-14, 0.0, 3.0e-13),  # (instances 0, 63, 64, 127)
+    "talos_cent_walk": (1.3e-12, 1.6e-11, 6.3e-14, 0.0, 1.7e-12),
+    "talos_cent_tight": (5.1e-13, 8.3e-13, 3.3e-14, 9.3e-8, 1.4e-13),
+    "talos_cent_h100": (6.7e-11, 4.1e-10, 8.9e-12, 0.0, 3.1e-11),
 }
 
 
 def gate(scenario):
-    """(dxs, dus, Ks) gates of a scenario: 10 x its measured floor, 1e-11 where the floor is below 1e-12."""
+    """(dxs, dus, Ks[, dvs, dlams]) gates of a scenario: 10 x its measured floor, 1e-11 where the floor is below 1e-12."""
     return tuple(1e-11 if f < 1e-12 else 10.0 * f for f in FLOORS[scenario])
 
 
 def _table():
-    rows = ["  %-34s floor %8.1e %8.1e %8.1e   gate %8.1e %8.1e %8.1e" % ((k,) + tuple(v) + gate(k)) for k, v in FLOORS.items()]
+    e = lambda v: " ".join("%8.1e" % x for x in v)
+    rows = ["  %-34s floor %s   gate %s" % (k, e(v), e(gate(k))) for k, v in FLOORS.items()]
     return "\n".join(rows)
 
 
@@ -174,7 +203,13 @@ def kind_of(gm):
         if ocp.settings.get("force_cone", False) or ocp.settings.get("land_cstr", False):
             raise ValueError("sweep_check: force_cone / land_cstr rows of the structured kinodynamics sweep are not in debug_lq's C")
         return "kino"
-    raise ValueError("sweep_check: the handle has no knot accessor (centroidal)")
+    if isinstance(ocp, simple_mpc.CentroidalOCP):
+        return "cent6" if int(ocp.settings.get("force_size", 3)) == 6 else "cent"
+    raise ValueError("sweep_check: the handle has no knot accessor")
+
+
+def is_cent(gm):
+    return kind_of(gm) in ("cent", "cent6")
 
 
 def knots(gm, inst):
@@ -192,6 +227,15 @@ def lq_inputs(gm, inst, kn=None, unfold_vel=False):
     Cm, D = np.zeros((H, nc, ndx)), np.zeros((H, nc, nu))
     if kind == "kino":
         Cm = st("C")
+    elif kind in ("cent", "cent6"):
+        for t, g in enumerate(kn):
+            act = g["act"]
+            assert np.all((act == 0.0) | (act == 1.0))
+            assert not g["Dd"][act == 0.0].any(), ("an inactive cone row must be a zero row", t)
+            D[t] = g["Dd"]
+            if kind == "cent6":
+                assert not g["Cd"][act == 0.0].any(), ("an inactive cone row must be a zero row", t)
+                Cm[t] = g["Cd"]
     else:
         nvel = kn[0]["Cv"].shape[0] if kind == "kino6" else 0
         ncd = kn[0]["Cd"].shape[0]
@@ -227,48 +271,89 @@ def stage_gaps(a, b):
     return out
 
 
-def references(lq, k_stages=None, sparse=True):
-    """Both CPU solves: (dx, du, K) of oracle_lib.riccati and (dx, du, {t: K_t}) of the KKT system."""
-    rx, ru, _, rl, rK = O.riccati(*lq)
-    kx, ku, _, _ = dense_kkt(*lq, sparse=sparse)
+def references(lq, k_stages=None, sparse=True, duals=False):
+    """Both CPU solves: (dx, du, K, dlam) of oracle_lib.riccati and (dx, du, {t: K_t}) of the KKT system; with `duals` a third entry, the
+    multiplier steps (dnu, dlam) of the Riccati solve and (dnu, dlam) of the KKT system."""
+    rx, ru, rv, rl, rK = O.riccati(*lq)
+    kx, ku, kv, kl = dense_kkt(*lq, sparse=sparse)
     H = ru.shape[0]
     ks = sorted({0, H // 2, H - 1}) if k_stages is None else k_stages
     kK = {t: kkt_gain(lq, t) for t in ks}
+    if duals:
+        return (rx, ru, rK, rl), (kx, ku, kK), ((rv, rl), (kv, kl))
     return (rx, ru, rK, rl), (kx, ku, kK)
 
 
+def _ref_gaps(lq, cent, k_stages=None):
+    """Both references of one instance and their mutual per-quantity gap (3 entries; 5 for the centroidal kinds)."""
+    if not cent:
+        ref, kkt = references(lq, k_stages)
+        dual = None
+    else:
+        ref, kkt, dual = references(lq, range(lq[6].shape[0]) if k_stages is None else k_stages, duals=True)
+    (rx, ru, rK, _), (kx, ku, kK) = ref, kkt
+    g = [stage_gaps(kx, rx).max(), stage_gaps(ku, ru).max(), max(stage_gaps(kK[t][None], rK[t][None]).max() for t in kK)]
+    if cent:
+        (rv, rl), (kv, kl) = dual
+        g += [stage_gaps(kv, rv).max(), stage_gaps(kl, rl).max()]
+    return ref, kkt, dual, np.array(g)
+
+
 def floors(gm, insts=None, k_stages=None):
-    """Mutual gap of the two CPU references on the device's knots: (dxs, dus, Ks), the largest stage of the largest instance."""
-    out = np.zeros(3)
+    """Mutual gap of the two CPU references on the device's knots: (dxs, dus, Ks) -- centroidal kinds: (dxs, dus, Ks, dvs, dlams), Ks at every
+    stage -- the largest stage of the largest instance."""
+    cent = is_cent(gm)
+    out = np.zeros(5 if cent else 3)
     for b in range(gm.B) if insts is None else insts:
-        lq = lq_inputs(gm, b)
-        (rx, ru, rK, _), (kx, ku, kK) = references(lq, k_stages)
-        g = [stage_gaps(kx, rx).max(), stage_gaps(ku, ru).max(), max(stage_gaps(kK[t][None], rK[t][None]).max() for t in kK)]
-        out = np.maximum(out, g)
+        out = np.maximum(out, _ref_gaps(lq_inputs(gm, b), cent, k_stages)[3])
     return tuple(out)
 
 
-def check(gm, scenario, insts=None, label=""):
-    """Device step and gains of every stage against oracle_lib.riccati on the device's own knots, gated by gate(scenario); prints the
-    observed gaps (and the floor of this run) so that a run records them.  Returns the per-instance (lq, reference, knots) for further checks."""
-    gx, gu, gK = gate(scenario)
+def device_outputs(gm):
+    """What `check` compares: the step and the gains of the last iteration (centroidal kinds: the multiplier steps too)."""
     dxs, dus = gm.debug_steps()
-    Ks = gm.Ks
+    out = dict(dxs=dxs, dus=dus, Ks=gm.Ks)
+    if is_cent(gm):
+        out["dvs"], out["dlams"] = gm.debug_dual_steps()
+    return out
+
+
+def check(gm, scenario, insts=None, label="", outputs=None, solved=None):
+    """Device step and gains of every stage (centroidal kinds: and the multiplier steps dvs, dlams) against oracle_lib.riccati on the device's
+    own knots, gated by gate(scenario); prints the observed gaps (and the floor of this run) so that a run records them.  Returns the
+    per-instance (lq, reference, knots) for further checks.  `outputs`: compare these arrays in place of the handle's (device_outputs; the
+    checker's self-test hands in perturbed copies); `solved`: the return value of an earlier call on the same state, whose knots and CPU
+    solves are then reused."""
+    cent = is_cent(gm)
+    names = ("dxs", "dus", "Ks", "dvs", "dlams") if cent else ("dxs", "dus", "Ks")
+    gates = gate(scenario)
+    assert len(gates) == len(names), (scenario, "FLOORS row does not fit the handle kind")
+    out = device_outputs(gm) if outputs is None else outputs
     res = []
-    worst, floor = np.zeros(3), np.zeros(3)
-    for b in range(gm.B) if insts is None else insts:
-        kn = knots(gm, b)
-        lq = lq_inputs(gm, b, kn)
-        (rx, ru, rK, rl), (kx, ku, kK) = references(lq)
-        floor = np.maximum(floor, [stage_gaps(kx, rx).max(), stage_gaps(ku, ru).max(), max(stage_gaps(kK[t][None], rK[t][None]).max() for t in kK)])
+    worst, floor = np.zeros(len(names)), np.zeros(len(names))
+    for i, b in enumerate(range(gm.B) if insts is None else insts):
+        if solved is None:
+            kn = knots(gm, b)
+            lq = lq_inputs(gm, b, kn)
+            ref, kkt, dual, fl = _ref_gaps(lq, cent)
+        else:
+            sb, lq, ref, kn, _, kkt, dual, fl = solved[i]
+            assert sb == b
+        rx, ru, rK, rl = ref
+        floor = np.maximum(floor, fl)
         assert np.all(rx[0] == 0.0)
-        g = [stage_gaps(dxs[b], rx), stage_gaps(dus[b], ru), stage_gaps(Ks[b], rK)]
+        g = [stage_gaps(out["dxs"][b], rx), stage_gaps(out["dus"][b], ru), stage_gaps(out["Ks"][b], rK)]
+        if cent:
+            assert np.all(rl[0] == 0.0)
+            g += [stage_gaps(out["dvs"][b], dual[0][0]), stage_gaps(out["dlams"][b], rl)]
         worst = np.maximum(worst, [x.max() for x in g])
-        res.append((b, lq, (rx, ru, rK, rl), kn, g, (kx, ku)))
-    print("sweep_check %s%s: device vs riccati dxs %.2e dus %.2e Ks %.2e | gates %.1e %.1e %.1e | reference floor of this run %.2e %.2e %.2e"
-          % (scenario, label, *worst, gx, gu, gK, *floor))
-    for b, lq, ref, kn, g, _ in res:
-        for name, gap, lim in zip(("dxs", "dus", "Ks"), g, (gx, gu, gK)):
+        res.append((b, lq, ref, kn, g, kkt[:2], dual, fl))
+    e = lambda v: " ".join("%.2e" % x for x in v)
+    print("sweep_check %s%s: device vs riccati %s: %s | gates %s | reference floor of this run %s | multiples of the table's floor %s"
+          % (scenario, label, " ".join(names), e(worst), e(gates), e(floor), " ".join(("%.2g" % (w / f)) if f > 0 else "-" for w, f in zip(worst, FLOORS[scenario]))))
+    for r in res:
+        b, g = r[0], r[4]
+        for name, gap, lim in zip(names, g, gates):
             assert gap.max() < lim, (scenario, label, "instance %d" % b, name, "stage %d" % int(gap.argmax()), float(gap.max()), lim)
     return res
 
@@ -308,7 +393,7 @@ def check_rebuilt_rows(gm, scenario, res, label=""):
     dt = float(gm.settings["timestep"])
     dxs, dus = gm.debug_steps()
     worst = np.zeros(3)
-    for b, lq, (rx, ru, rK, rl), kn, _, _ in res:
+    for b, lq, (rx, ru, rK, rl), kn, *_ in res:
         A, B, mu = lq[5], lq[6], lq[13]
         for t in range(gm.H):
             dense = A[t] @ dxs[b, t] + B[t] @ dus[b, t]
@@ -357,7 +442,9 @@ def active_rows(gm, insts=None):
     nbox = nden = 0
     for b in range(gm.B) if insts is None else insts:
         for g in knots(gm, b):
-            if kind == "kino":
+            if kind in ("cent", "cent6"):
+                nden += int(g["act"].sum())
+            elif kind == "kino":
                 nbox += int((np.abs(g["C"][:12]).sum(1) > 0).sum())
             else:
                 ncd = g["Cd"].shape[0]

@@ -217,8 +217,13 @@ def test_handle_kinds_answer_foreign_entry_points(built, monkeypatch):
     # kinodynamics and full-dynamics handles
     expect(_INVALID, _KINO_ONLY, "smpc_get_x_device", c, 0, out)
     expect(_INVALID, b"the centroidal step is one fused kernel", "smpc_set_early_exit_on_tol", c, 1)
-    expect(_INVALID, _KINO_ONLY, "smpc_debug_get_lq", c, 0, 0, out)
-    expect(_INVALID, _KINO_ONLY, "smpc_debug_get_terminal", c, 0, out, out2)
+    # (centroidal handles answer the knot read-outs: tests/test_centroidal_knots.py) ; the multiplier steps are theirs alone
+    assert _answer(R, "smpc_debug_get_lq", c, 0, 0, out)[0] == 0 and _answer(R, "smpc_debug_get_terminal", c, 0, out, out2)[0] == 0
+    expect(_INVALID, b"Stage index exceeds stage vector size", "smpc_debug_get_lq", c, 0, H, out)
+    expect(_INVALID, b"instance index out of range", "smpc_debug_get_terminal", c, 1, out, out2)
+    assert _answer(R, "smpc_debug_get_dual_steps", c, out, out2)[0] == 0
+    for h in (k, f):
+        expect(_INVALID, b"smpc_debug_get_dual_steps needs a centroidal handle", "smpc_debug_get_dual_steps", h, out, out2)
     mask = (C.c_uint * 1)(15)
     expect(_INVALID, b"smpc_full_forward_dynamics needs a kinodynamics or a full-dynamics handle", "smpc_full_forward_dynamics", c, 1, out, out,
            mask, None, None, C.c_double(0), C.c_double(0), 0, out, out2, None, None)
@@ -234,9 +239,10 @@ def test_handle_kinds_answer_foreign_entry_points(built, monkeypatch):
     for h in (k, c):
         expect(_INVALID, b"(set SMPC_PHASE_PROFILE=1 before smpc_create)", "smpc_debug_get_phase_cycles", h, out)
     expect(_RUNTIME, b"(set SMPC_PHASE_PROFILE=1 before smpc_create_fulldynamics)", "smpc_debug_get_phase_cycles", f, out)
-    # smpc_lq_size: the row-major kinodynamics knot unless the handle is a full-dynamics one
+    # smpc_lq_size: the row-major kinodynamics knot for a kinodynamics and for a null handle ; the full-dynamics knot ; the unpacked record of
+    # a point-foot centroidal handle (A 81, B 108, Q 81, S 108, R 144, Dd 96, q 9, r 12, f 9, d 8, act 8, any, preg)
     nk = R.smpc_lq_size(k)
-    assert nk == 6000 and R.smpc_lq_size(c) == nk and R.smpc_lq_size(None) == nk and R.smpc_lq_size(f) == 3848
+    assert nk == 6000 and R.smpc_lq_size(None) == nk and R.smpc_lq_size(f) == 3848 and R.smpc_lq_size(c) == 666
     # a controller of the other family
     kw = dict(kp_base=10.0, kp_posture=1.0, kp_contact=10.0, w_base=10.0, w_posture=0.1, w_contact_force=1e-3, w_contact_motion=1.0)
     s = O.id_settings(rb, 1e-3, admm_iters=10, admm_tol=-1.0, **kw)
@@ -304,6 +310,7 @@ def test_null_handle_is_an_invalid_argument_everywhere(built):
     assert _answer(R, "smpc_debug_get_lq", None, 0, 0, out) == (_INVALID, b"null argument")
     assert _answer(R, "smpc_debug_get_steps", None, out, out) == (_INVALID, b"null argument")
     assert _answer(R, "smpc_debug_get_terminal", None, 0, out, out) == (_INVALID, b"null argument")
+    assert _answer(R, "smpc_debug_get_dual_steps", None, out, out) == (_INVALID, b"null argument")
     assert _answer(R, "smpc_get_cold_trace", None, out, 4) == (_INVALID, b"null argument")
     assert _answer(R, "smpc_set_profiling", None, 1) == (_INVALID, b"null argument")
     assert _answer(R, "smpc_reset_kernel_times", None) == (_INVALID, b"null argument")

@@ -193,8 +193,9 @@ def test_centroidal_handle_surface(lib):
         gm.ocp_handler.createProblem(np.zeros(9), 50, 6, -9.81)
     with pytest.raises(RuntimeError, match="generateCycleHorizon"):
         gm.iterate(rb.x_ref[None, :])
-    with pytest.raises(RuntimeError, match="kinodynamics handle"):
-        gm.debug_lq(0, 0)
+    assert gm.debug_lq(0, 0)["A"].shape == (9, 9)  # (the knot read-out of centroidal handles: tests/test_centroidal_knots.py)
+    with pytest.raises(RuntimeError, match="Stage index exceeds stage vector size"):
+        gm.debug_lq(0, 50)
     fe = gm.updateInternalData(rb.x_ref[None, :])  # the front-end of the handle (getCentroidalState of the measured state)
     assert np.allclose(fe["centroidal_state"][0, :3], rb.centroidal(rb.x_ref)["com"], atol=1e-12) and np.allclose(fe["hg"], 0)
     with pytest.raises(RuntimeError, match="shape"):

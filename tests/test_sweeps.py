@@ -1,4 +1,5 @@
-"""Each Riccati sweep (riccati_kino_body, riccati_dense_body<...>, forward_kino_body, forward_full_body) against CPU solves of its own knots
+"""Each Riccati sweep (riccati_kino_body, riccati_dense_body<...>, forward_kino_body, forward_full_body, and the centroidal ones: cent_bwd_body /
+cent_fwd_body of the point-foot pipeline, riccati_dense_body<Cent6Dims> / cent6_forward_body of 6-D feet) against CPU solves of its own knots
 (tests/sweep_check.py): step and gains of ALL stages, per stage and per quantity, at gates of 10 x the measured disagreement of the two CPU
 references.  The same bodies run on the emulated kernel bodies (CPU tier) and on the device (-m gpu).  Also here: the single-writer invariant of
 the dense cone rows behind O_cdirty, and the rows of [A B] the forward sweep rebuilds."""
@@ -133,6 +134,159 @@ def _talos_kino(lib):
     yield "", gm
 
 
+# ---- centroidal scenarios.  Generators of (label, gm, om): om is the oracle run on the same measured states when `paired` (the knot parity
+#      of tests/test_centroidal_knots.py), else None.  The measured multibody state drifts as a simulator would report it. ----
+CENT_HARD = dict(settings_override=dict(mu=0.1), walk=(0.8, 0.5, 0, 0, 0, 0.5))  # (HARD of tests/test_centroidal_mpc.py)
+CENT_HARD_SEED = 20240529
+TWO_PARTS_INSTS = (0, 63, 64, 127)
+
+
+def _go2_cent(lib, B, iters, horizon=50, cycle=None, walk=WALK, paired=False, env=None, **kw):
+    """env: switches of the engine (SMPC_CENT_PARTS; SMPC_CENT_FUSED of a cross-check build), which it reads when the handle is created."""
+    names = ("SMPC_CENT_FUSED", "SMPC_CENT_LS", "SMPC_CENT_PARTS")
+    old = {k: os.environ.pop(k, None) for k in names}
+    try:
+        os.environ.update(env or {})
+        gm, rb, _, _ = S.make_cent_product(B, iters, lib, horizon, **kw)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+    om = S.make_cent_oracle(B, iters, horizon, **kw)[0] if paired else None
+    for m in (gm, om):
+        if m is not None:
+            m.generateCycleHorizon(O.trot_cycle() if cycle is None else cycle)
+            m.switchToWalk(np.array(walk, float))
+    if om is not None:
+        om.keep_knots()
+    return gm, om, rb
+
+
+def _cent_steps(gm, om, rb, X, n):
+    nv = rb.nv
+    for _ in range(n):
+        gm.iterate(X)
+        if om is not None:
+            om.iterate(X)
+        X = np.stack([rb.integrate(x, np.r_[np.zeros(nv), 0.02, 0.01, np.zeros(nv - 2)]) for x in X])
+    return X
+
+
+def _cent_record(lib, iters, paired=False):
+    """Settings of record, H = 50, short trot (4 double / 8 single).  Checked at control steps 3, 6, 14 (ring head 3, 6, 14; the contact changes
+    of the cycle are inside the horizon) and at 56 and 64: the cycle enters at the far end of the horizon, so stage 0 has its take-off at
+    control step 54 and its touch-down at 62 (ring head 5 and 13: the ring has wrapped)."""
+    gm, om, rb = _go2_cent(lib, 2, iters, cycle=O.trot_cycle(T_ds=4, T_ss=8), mpc_override=dict(T_fly=8, T_contact=4), paired=paired)
+    X = S.random_states(rb, 2)
+    done = 0
+    masks = []
+    for at in (3, 6, 14, 56, 64):
+        X = _cent_steps(gm, om, rb, X, at - done)
+        done = at
+        masks.append(sum(gm.ocp_handler.getContactState(0)))
+        yield " step %d" % at, gm, om
+    assert masks == [4, 4, 4, 2, 4], ("stage 0 must have passed a take-off and a touch-down", masks)
+
+
+def _cent_cones(lib, paired=False):
+    """Active friction-cone rows and backtracking: the [Z z] rows of cent_bwd_body, the `any` branch of cent_fwd_body, both pivot panels."""
+    kw = dict(CENT_HARD)
+    gm, om, rb = _go2_cent(lib, 2, 2, walk=kw.pop("walk"), paired=paired, **kw)
+    X = S.random_states(rb, 2, seed=CENT_HARD_SEED, scale=2.0)
+    nact, lo, hi, mixed, back = 0, 0, 0, False, False
+    for step in range(4):
+        X = _cent_steps(gm, om, rb, X, 1)
+        for b in range(2):
+            kn = SC.knots(gm, b)
+            act = np.stack([g["act"] for g in kn])
+            anys = np.array([g["any"] for g in kn])
+            assert np.array_equal(anys != 0.0, act.any(1)), "the record's flag must say whether a cone row of the stage is active"
+            nact += int(act.sum())
+            lo += int(act[:, :4].sum())
+            hi += int(act[:, 4:].sum())
+            mixed = mixed or (anys.any() and not anys.all())
+        back = back or bool((gm.info[:, 2] < 1.0).any())
+        yield " step %d" % step, gm, om
+    assert nact >= 10, ("the scenario must hold active cone rows", nact)
+    assert lo > 0 and hi > 0, ("active rows in both pivot panels (rows 0..3 -> nu_a, 4..7 -> nu_b)", lo, hi)
+    assert mixed, "one instance must hold stages with and without an active cone row"
+    assert back, "at least one instance must have taken alpha < 1"
+
+
+def _cent_horizon(lib, horizon, paired=False):
+    gm, om, rb = _go2_cent(lib, 2, 2, horizon=horizon, paired=paired)
+    _cent_steps(gm, om, rb, S.random_states(rb, 2), 3)
+    yield "", gm, om
+
+
+def _cent_dense_w(lib, paired=False):
+    """The dense weights and CoM reference of test_centroidal_mpc.py::test_emu_dense_weights_and_com_reference."""
+    rng = np.random.default_rng(4)
+
+    def spd(n, s):
+        a = rng.normal(size=(n, n))
+        return s * (a @ a.T / n + np.eye(n))
+
+    ov = dict(w_u=spd(12, 1e-3), w_com=spd(3, 10.0), w_linear_mom=spd(3, 1.0), w_angular_mom=spd(3, 5.0), w_linear_acc=spd(3, 0.01),
+              w_angular_acc=spd(3, 0.01))
+    gm, om, rb = _go2_cent(lib, 2, 2, settings_override=ov, paired=paired)
+    xr = np.r_[0.02, -0.01, 0.31, np.zeros(6)]
+    gm.x_reference = xr
+    if om is not None:
+        om.set_x_reference(xr)
+    _cent_steps(gm, om, rb, S.random_states(rb, 2), 4)
+    yield "", gm, om
+
+
+def _cent_two_parts(lib):
+    """B = 128 as two parts of 64 on two streams (record and ring addressing across inst0).  The engine splits by itself from B = 1024 on;
+    at this batch SMPC_CENT_PARTS = 2 asks for it (read when the handle is created)."""
+    gm, om, rb = _go2_cent(lib, 128, 1, env={"SMPC_CENT_PARTS": "2"})
+    _cent_steps(gm, om, rb, S.random_states(rb, 128), 3)
+    yield "", gm, om
+
+
+def _talos_cent(lib, tight, horizon=20, paired=False):
+    kw = dict(SHORT) if horizon == 20 else dict(horizon=horizon, cycle=O.walk_cycle(), mpc_override=None)
+    walk = TALOS_TURN if tight else (0.1, 0, 0, 0, 0, 0)
+    ov = TALOS_TIGHT if tight else None
+    if paired:
+        om, gm, rb = S.make_talos_cent_pair(2, max_iters=2, lib=lib, walk=walk, settings_override=ov, **kw)
+        om.keep_knots()
+    else:
+        cyc = kw.pop("cycle")
+        om = None
+        gm, rb, _, _ = S.make_talos_cent_product(2, max_iters=2, lib=lib, settings_override=ov, **kw)
+        gm.generateCycleHorizon(cyc)
+        gm.switchToWalk(np.array(walk, float))
+    _cent_steps(gm, om, rb, S.talos_random_states(rb, 2, scale=0.7), 6 if tight else 3)
+    if tight:
+        _, nden = SC.active_rows(gm)
+        assert nden >= 20, ("the scenario must hold active wrench-cone rows", nden)
+    yield "", gm, om
+
+
+CENT_SCENARIOS = {
+    "cent_record_k1": lambda lib, **kw: _cent_record(lib, 1, **kw),
+    "cent_record_k3": lambda lib, **kw: _cent_record(lib, 3, **kw),
+    "cent_cones_backtrack": _cent_cones,
+    "cent_h2": lambda lib, **kw: _cent_horizon(lib, 2, **kw),
+    "cent_h63": lambda lib, **kw: _cent_horizon(lib, 63, **kw),  # the last horizon of the polynomial line search (H + 1 <= 64)
+    "cent_h65": lambda lib, **kw: _cent_horizon(lib, 65, **kw),  # the first whose pre-pass needs more than one lane per stage slot
+    "cent_dense_w": _cent_dense_w,
+    "cent_two_parts": _cent_two_parts,
+    "talos_cent_walk": lambda lib, **kw: _talos_cent(lib, False, **kw),
+    "talos_cent_tight": lambda lib, **kw: _talos_cent(lib, True, **kw),
+    "talos_cent_h100": lambda lib, **kw: _talos_cent(lib, False, 100, **kw),  # the device only
+}
+CENT_INSTS = {"cent_two_parts": TWO_PARTS_INSTS}
+
+
+def _unpaired(gen):
+    return lambda lib: ((label, gm) for label, gm, _ in gen(lib))
+
+
 SCENARIOS = {
     "kino_record_k1": lambda lib: _kino_record(lib, 1),
     "kino_record_k3": lambda lib: _kino_record(lib, 3),
@@ -148,13 +302,17 @@ SCENARIOS = {
     "talos_kino_cone": _talos_kino,
     "talos_walk_h100": lambda lib: _talos(lib, False, 100),  # the device only
 }
-CPU_SCENARIOS = [k for k in SCENARIOS if k != "talos_walk_h100"]
+SCENARIOS.update({k: _unpaired(v) for k, v in CENT_SCENARIOS.items()})
+CPU_SCENARIOS = [k for k in SCENARIOS if k not in ("talos_walk_h100", "talos_cent_h100")]
 
 
 def _body(name, lib, scenario=None):
     """Runs a scenario and checks it at every yielded control step; returns the device step (dxs, dus) of the last one."""
     for label, gm in SCENARIOS[name](lib):
-        res = SC.check(gm, scenario or name, label=label)
+        res = SC.check(gm, scenario or name, insts=CENT_INSTS.get(name), label=label)
+        if SC.is_cent(gm):
+            steps = gm.debug_steps()
+            continue
         if SC.kind_of(gm) != "kino":
             SC.check_rebuilt_rows(gm, scenario or name, res, label)
         if SC.kind_of(gm) == "kino6":
@@ -194,6 +352,33 @@ def test_emulated_dense_sweep_of_kinodynamics_solves_its_knots(built, tmp_path):
 @pytest.mark.parametrize("name", list(SCENARIOS))
 def test_hip_sweeps_solve_their_knots(built, name):
     _body(name, None)
+
+
+def test_checker_raises_on_one_perturbed_entry(built):
+    """Self-test of SC.check on cent_record_k1 (emulated bodies; the checker itself is CPU code): the outputs as they are pass; a copy with ONE
+    entry moved by 100 x its gate, relative to that stage's block, must raise -- a gain entry at a middle stage, a dvs entry in a stage with an
+    active cone row, a dus entry at stage H - 1."""
+    name = "cent_record_k1"
+    gates = dict(zip(("dxs", "dus", "Ks", "dvs", "dlams"), SC.gate(name)))
+    found = None
+    for label, gm in SCENARIOS[name](S.emu_lib()):
+        acts = [(b, t) for b in range(gm.B) for t, g in enumerate(SC.knots(gm, b)) if g["act"].any()]
+        if acts and found is None:
+            found = label
+            out = SC.device_outputs(gm)
+            res = SC.check(gm, name, label=label, outputs={k: v.copy() for k, v in out.items()})
+            H = gm.H
+            b, t = acts[0]
+            row = int(np.flatnonzero(SC.knots(gm, b)[t]["act"])[0])
+            for key, idx in (("Ks", (1, H // 2, 5, 4)), ("dvs", (b, t, row)), ("dus", (0, H - 1, 7))):
+                pert = {k: v.copy() for k, v in out.items()}
+                block = np.abs(out[key][idx[:2]]).max()
+                assert block > 0.0
+                pert[key][idx] += 100.0 * gates[key] * block
+                with pytest.raises(AssertionError) as err:
+                    SC.check(gm, name, label=label + " perturbed " + key, outputs=pert, solved=res)
+                assert err.value.args[0][3] == key and err.value.args[0][4] == "stage %d" % idx[1], err.value.args
+    assert found is not None, "cent_record_k1 must hold a stage with an active cone row at one of its checked steps"
 
 
 # ---- the dense cone rows of the knot behind O_cdirty ----
@@ -243,8 +428,7 @@ def _cdirty_talos_full(lib, steps):
 
 
 def _cdirty_talos_kino(lib, steps):
-    """Stands in for the centroidal handle, which has no knot accessor: the kinodynamics variant's cone rows are constant rows of Dd (Cd = 0).
-    The oracle exports no D rows, so "active rows equal the oracle's" is not checked here: the parity of Dd (which rows are present, against
+    """The kinodynamics variant's cone rows are constant rows of Dd (Cd = 0).  "Active rows equal the oracle's" is not checked here: the parity of Dd (which rows are present, against
     the activity flags) stays with test_talos_kinodynamics.py::test_emulated_kernels_stage_knots; this test holds the flag, the zero block and
     the active -> inactive -> active transition."""
     kw = dict(SHORT)
