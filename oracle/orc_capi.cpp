@@ -136,6 +136,17 @@ namespace
     o += k.D.a.size();
     return (int)(o - out);
   }
+  // terminal node of the last iteration of instance b (after keep_knots): QN [ndx][ndx], qN [ndx], the iteration's preg
+  template <class MPC>
+  int mpc_get_terminal_impl(MPC * m, int b, double * QN, double * qN, double * preg)
+  {
+    if (b < 0 || b >= (int)m->last_term.size() || m->last_term[b].QN.a.empty())
+      return -1;
+    mat_to(m->last_term[b].QN, QN);
+    vec_to(m->last_term[b].qN, qN);
+    *preg = m->last_term[b].preg;
+    return 0;
+  }
   // ProxDDP on an H-stage problem with per-stage references, run to convergence with the stopping rules of the cold solve (orc_mpc.hpp) --
   // for the checks of the converged answer against an independent NLP solver (tests/test_oracle_vs_scipy.py).
   // trace: [iter][6] = prim_infeas, dual_infeas, cost, phi0, alpha, ls_failed.  Returns the iteration count.
@@ -790,7 +801,13 @@ extern "C"
     BatchMPC * m = (BatchMPC *)h;
     m->keep_knots = on != 0;
     m->last_knots.assign(m->B, std::vector<Knot>());
+    m->last_term.assign(m->B, TermKnot());
   }
+  void orc_mpc_set_iterate(void * h, const double * xs, const double * us, const double * vs, const double * lams)
+  {
+    ((BatchMPC *)h)->set_iterate(xs, us, vs, lams);
+  }
+  int orc_mpc_get_terminal(void * h, int b, double * QN, double * qN, double * preg) { return mpc_get_terminal_impl((BatchMPC *)h, b, QN, qN, preg); }
   int orc_mpc_get_knot(void * h, int b, int t, double * out) { return mpc_get_knot_impl((BatchMPC *)h, b, t, out); }
   int orc_mpc_cold_iters(void * h) { return (int)((BatchMPC *)h)->cold_trace.size(); }
   void orc_mpc_cold_trace(void * h, double * out) // [n][4]: phi0, prim, dual, alpha
@@ -861,7 +878,13 @@ extern "C"
     BatchMPCFull * m = (BatchMPCFull *)h;
     m->keep_knots = on != 0;
     m->last_knots.assign(m->B, std::vector<Knot>());
+    m->last_term.assign(m->B, TermKnot());
   }
+  void orc_fmpc_set_iterate(void * h, const double * xs, const double * us, const double * vs, const double * lams)
+  {
+    ((BatchMPCFull *)h)->set_iterate(xs, us, vs, lams);
+  }
+  int orc_fmpc_get_terminal(void * h, int b, double * QN, double * qN, double * preg) { return mpc_get_terminal_impl((BatchMPCFull *)h, b, QN, qN, preg); }
   int orc_fmpc_get_knot(void * h, int b, int t, double * out) { return mpc_get_knot_impl((BatchMPCFull *)h, b, t, out); }
   int orc_fmpc_cold_iters(void * h) { return (int)((BatchMPCFull *)h)->cold_trace.size(); }
   void orc_fmpc_cold_trace(void * h, double * out) // [n][4]: phi0, prim, dual, alpha

@@ -145,6 +145,7 @@ namespace orc
     std::vector<IterInfo> last_info;
     bool keep_knots = false;
     std::vector<std::vector<Knot>> last_knots; // [b][t], filled when keep_knots (tests only)
+    std::vector<TermKnot> last_term;           // [b], filled when keep_knots (tests only)
 
     bool terminal_constraint = false;
     BatchMPCT(const smpc_robot_model * m, const ModelSettings & ks, const MPCSettings & ms, int H_, int B_, double gravity_arg,
@@ -221,6 +222,25 @@ namespace orc
     }
     std::vector<IterInfo> cold_trace;
     bool early_exit_on_tol = false; // SolverProxDDP::run's convergence test inside iterate (reference src/mpc.cpp:43,212)
+    // (tests only) overwrite the iterate of every instance: xs [B][H+1][nx], us [B][H][nu], vs [B][H][nc], lams [B][H+1][ndx].  Timers, foot
+    // trajectories, references and the terminal multiplier stay as they are.
+    void set_iterate(const double * xs, const double * us, const double * vs, const double * lams)
+    {
+      for (int b = 0; b < B; b++)
+      {
+        SolverState & S = sol[b];
+        for (int t = 0; t <= H; t++)
+        {
+          S.xs[t].assign(xs + ((size_t)b * (H + 1) + t) * md.nx, xs + ((size_t)b * (H + 1) + t + 1) * md.nx);
+          S.lams[t].assign(lams + ((size_t)b * (H + 1) + t) * md.ndx, lams + ((size_t)b * (H + 1) + t + 1) * md.ndx);
+        }
+        for (int t = 0; t < H; t++)
+        {
+          S.us[t].assign(us + ((size_t)b * H + t) * md.nu, us + ((size_t)b * H + t + 1) * md.nu);
+          S.vs[t].assign(vs + ((size_t)b * H + t) * md.nc, vs + ((size_t)b * H + t + 1) * md.nc);
+        }
+      }
+    }
     void set_velocity_all(const double * v6)
     {
       for (auto & v : vbase_inst)
@@ -397,7 +417,8 @@ namespace orc
         S.preg = SolverConsts::REG_INIT; // regularisation restarts with every solver run
         for (int it = 0; it < st.max_iters; it++)
         {
-          last_info[b] = solver.iterate(R, o, S, vs_e, lams_e, keep_knots ? &last_knots[b] : nullptr, &vN_e, early_exit_on_tol ? st.TOL : -1.0);
+          last_info[b] = solver.iterate(R, o, S, vs_e, lams_e, keep_knots ? &last_knots[b] : nullptr, &vN_e, early_exit_on_tol ? st.TOL : -1.0,
+                                        keep_knots ? &last_term[b] : nullptr);
           if (early_exit_on_tol && std::fmax(last_info[b].prim_infeas, last_info[b].dual_infeas) <= st.TOL)
             break;
         }

@@ -190,6 +190,9 @@ def lib():
     L.orc_cmpc_get_terminal.argtypes = [vp, C.c_int, _dp, _dp, _dp]
     L.orc_mpc_keep_knots.argtypes = [vp, C.c_int]
     L.orc_mpc_get_knot.argtypes = [vp, C.c_int, C.c_int, _dp]
+    for _p in ("orc_mpc_", "orc_fmpc_"):
+        getattr(L, _p + "set_iterate").argtypes = [vp, _dp, _dp, _dp, _dp]
+        getattr(L, _p + "get_terminal").argtypes = [vp, C.c_int, _dp, _dp, _dp]
     L.orc_centroidal_dynamics.argtypes = [C.c_double, _dp, C.c_double, C.c_int, _dp, _dp, _bp, _dp, _dp, _dp, _dp]
     L.orc_friction.argtypes = [_dp, _dp, C.c_int, _dp, _dp, C.c_int]
     L.orc_interpolate.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, _dp, C.c_int, C.c_int, _dp]
@@ -575,6 +578,7 @@ class OracleMPC:
         self.nx_in = kino.nx
         self.B = B
         self.H = mpc_settings["T"]
+        self.mu = float(mpc_settings["mu_init"])
         s = MpcSettingsC(
             mpc_settings["swing_apex"], mpc_settings["support_force"], mpc_settings["TOL"], mpc_settings["mu_init"],
             mpc_settings["timestep"], mpc_settings["max_iters"], mpc_settings.get("num_threads", 0),
@@ -676,6 +680,25 @@ class OracleMPC:
             res[name] = out[o : o + sz].reshape(shape).copy()
             o += sz
         return res
+
+    def set_iterate(self, xs, us, vs, lams):
+        """Overwrite the iterate of every instance (shapes and row order of the product's xs, us, vs, lams); timers, foot trajectories and
+        references stay.  For evaluating the next iteration at another solver's point (tests/knot_check.py)."""
+        k = self.kino
+        arrs = []
+        for a, shape in ((xs, (self.B, self.H + 1, k.nx)), (us, (self.B, self.H, k.nu)), (vs, (self.B, self.H, k.nc)), (lams, (self.B, self.H + 1, k.ndx))):
+            a = np.ascontiguousarray(a, float)
+            assert a.shape == shape, (a.shape, shape)
+            arrs.append(a)
+        self._f("set_iterate")(self.h, *arrs)
+
+    def terminal_knot(self, b):
+        """(QN, qN, preg) of the last iteration of instance b: the terminal node the Riccati recursion started from and the primal
+        regularisation the iteration's knots carry (after keep_knots())."""
+        n = self.kino.ndx
+        QN, qN, preg = np.zeros((n, n)), np.zeros(n), np.zeros(1)
+        assert self._f("get_terminal")(self.h, b, QN, qN, preg) == 0
+        return QN, qN, float(preg[0])
 
     def cold_trace(self):
         n = self._f("cold_iters")(self.h)
@@ -792,13 +815,8 @@ class OracleCentMPC(OracleMPC):
     def xdot(self):
         return self._get(7, (self.B, self.H, 18))[:, :, :9]
 
-    def terminal_knot(self, b):
-        """(QN, qN, preg) of the last iteration of instance b: the terminal node the Riccati recursion started from and the primal
-        regularisation the iteration's knots carry (after keep_knots())."""
-        n = self.kino.ndx
-        QN, qN, preg = np.zeros((n, n)), np.zeros(n), np.zeros(1)
-        assert lib().orc_cmpc_get_terminal(self.h, b, QN, qN, preg) == 0
-        return QN, qN, float(preg[0])
+    def set_iterate(self, xs, us, vs, lams):
+        raise NotImplementedError("set_iterate: kinodynamics and full-dynamics handles only")
 
 
 class OracleFullMPC(OracleMPC):

@@ -38,7 +38,9 @@ def _steps(gm, X, n):
 
 # ---- scenarios: generators of (label, gm) at every control step that is checked ----
 def _kino_record(lib, iters):
-    """Settings of record, short trot (4 double / 8 single): stage 0 passes a take-off at control step 4 and a touch-down at step 12."""
+    """Settings of record, short trot (4 double / 8 single), checked at control steps 3, 6, 14.  The cycle enters at the far end of the horizon:
+    a take-off is inside the horizon from control step 5 on, a touch-down from step 13 on; stage 0 itself stays in full contact until step 54
+    (tests/test_knots.py::_kino_record asserts the contact masks; as _cent_record below spells out)."""
     gm, rb = _go2_kino(lib, 2, iters, cycle=O.trot_cycle(T_ds=4, T_ss=8), mpc_override=dict(T_fly=8, T_contact=4))
     X = S.random_states(rb, 2)
     done = 0
