@@ -268,7 +268,125 @@ namespace simple_mpc
       return r;
     }
 
+    // ---- effort limits, joint damping, armature and joint-limit stops (smpc_robot_sim_set_joint_model and the entries after it) ----
+    // The arrays of a joint model: each empty (tau_max = inf, damping = armature = 0, the limits of the robot table), [na] (broadcast over
+    // the batch) or [rows][na] (per robot), na = nv - 6.  activation (rad; 0 stands for 0.1): the distance to a limit below which a joint
+    // gets a stop row (at most 8 per robot and step); stop_erp (0 stands for 0.2): the part of a penetration removed per step.
+    struct JointModel
+    {
+      std::vector<double> tau_max, damping, armature, q_lo, q_hi;
+      bool stops = true;
+      double activation = 0.0, stop_erp = 0.0;
+    };
+    // From this call on stepGroundDevice clips the torques to [-tau_max, tau_max], damps the joints implicitly and holds them at their
+    // limits with unilateral rows that share the contact solve with the feet.  Needs setGround first; setGround called afterwards drops
+    // the model.
+    void setJointModel(const JointModel & model)
+    {
+      std::vector<double> keep[5];
+      const smpc_joint_model_settings m = jointModel(model, (size_t)batch_, keep);
+      check(smpc_robot_sim_set_joint_model(h_, &m));
+    }
+    // the torques applied in the last ground step [B][na] (host copy; joins the handle's stream); zeros before setJointModel
+    std::vector<double> lastAppliedTorques()
+    {
+      std::vector<double> t((size_t)batch_ * (size_t)(nv_ - 6));
+      check(smpc_robot_sim_read_joint_last(h_, t.data(), nullptr, nullptr, nullptr));
+      return t;
+    }
+    struct JointStops
+    {
+      std::vector<int32_t> stop_rows, dropped; // [n][8]: +(k + 1) joint k at its lower stop, -(k + 1) at its upper stop, 0 unused; [n]
+      std::vector<double> lam_stop;            // [n][8]
+    };
+    JointStops lastJointStops()
+    {
+      JointStops s;
+      s.stop_rows.resize((size_t)batch_ * SMPC_JOINT_MAX_STOPS);
+      s.lam_stop.resize((size_t)batch_ * SMPC_JOINT_MAX_STOPS);
+      s.dropped.resize((size_t)batch_);
+      check(smpc_robot_sim_read_joint_last(h_, nullptr, s.stop_rows.data(), s.lam_stop.data(), s.dropped.data()));
+      return s;
+    }
+    // the same as device pointers owned by the handle (null before setJointModel; they change when setGround is called again)
+    void jointModelDevicePointers(double ** tau_applied_device, int32_t ** stop_rows_device, double ** lam_stop_device, int32_t ** dropped_device)
+    {
+      check(smpc_robot_sim_get_joint_last(h_, tau_applied_device, stop_rows_device, lam_stop_device, dropped_device));
+    }
+    struct GroundJoint
+    {
+      GroundSolve s;
+      std::vector<double> tau_applied; // [n][na]
+      JointStops stops;
+    };
+    // groundSolveDynamics with an explicit joint model per state; the handle's model, settings and buffers are neither read nor changed
+    GroundJoint groundJointDynamics(const std::vector<double> & X, const std::vector<double> & tau, double dt, const JointModel & model,
+                                    const std::vector<double> & planes = {}, const std::vector<double> & mu = {}, const std::vector<double> & push = {},
+                                    int joint = 0, const std::vector<double> & lam0 = {}, bool warm_start = true, double tol = 0.0, int min_sweeps = 0)
+    {
+      const size_t nx = (size_t)(nq_ + nv_), n = X.size() / nx, nr = 3 * (size_t)gn_, na = (size_t)(nv_ - 6);
+      if (n == 0 || X.size() != n * nx || tau.size() != n * na)
+        throw std::runtime_error("X [n][nq + nv], tau [n][nv - 6] expected");
+      if ((!planes.empty() && planes.size() != n * 4) || (!mu.empty() && mu.size() != n) || (!push.empty() && push.size() != n * 6))
+        throw std::runtime_error("planes [n][4], mu [n], push [n][6] expected (or empty)");
+      if (!lam0.empty() && lam0.size() != n * nr)
+        throw std::runtime_error("lam0 [n][3 points] expected (or empty)");
+      const smpc_ground_solver_settings s = {warm_start && !lam0.empty() ? 1 : 0, tol, min_sweeps};
+      std::vector<double> keep[5];
+      const smpc_joint_model_settings m = jointModel(model, n, keep);
+      GroundJoint r;
+      r.s.g.v_next.resize(n * nv_);
+      r.s.g.a.resize(n * nv_);
+      r.s.g.lambda.resize(n * nr);
+      r.s.g.gap.resize(n * (size_t)gn_);
+      r.s.g.contact.resize(n);
+      r.s.lambda_contact.resize(n * nr);
+      r.s.residual.resize(n);
+      r.s.sweeps.resize(n);
+      r.tau_applied.resize(n * na);
+      r.stops.stop_rows.resize(n * SMPC_JOINT_MAX_STOPS);
+      r.stops.lam_stop.resize(n * SMPC_JOINT_MAX_STOPS);
+      r.stops.dropped.resize(n);
+      check(smpc_robot_sim_ground_joint_dynamics(h_, (int)n, X.data(), tau.data(), dt, planes.empty() ? nullptr : planes.data(), mu.empty() ? nullptr : mu.data(),
+                                                 push.empty() ? nullptr : push.data(), joint, &s, lam0.empty() ? nullptr : lam0.data(), &m, r.s.g.v_next.data(),
+                                                 r.s.g.a.data(), r.s.g.lambda.data(), r.s.lambda_contact.data(), r.s.g.gap.data(), r.s.g.contact.data(),
+                                                 r.s.sweeps.data(), r.s.residual.data(), r.tau_applied.data(), r.stops.stop_rows.data(), r.stops.lam_stop.data(),
+                                                 r.stops.dropped.data()));
+      return r;
+    }
+
   private:
+    // the C struct of a JointModel for `rows` robots; with one per-robot array the broadcast ones are repeated into `keep` (one stride per call)
+    smpc_joint_model_settings jointModel(const JointModel & model, size_t rows, std::vector<double> (&keep)[5]) const
+    {
+      const size_t na = (size_t)(nv_ - 6);
+      const std::vector<double> * src[5] = {&model.tau_max, &model.damping, &model.armature, &model.q_lo, &model.q_hi};
+      static const char * const names[5] = {"tau_max", "damping", "armature", "q_lo", "q_hi"};
+      bool per_robot = false;
+      for (int a = 0; a < 5; a++)
+      {
+        const size_t sz = src[a]->size();
+        if (sz != 0 && sz != na && sz != rows * na)
+          throw std::runtime_error(std::string(names[a]) + " [na] or [rows][na] expected (or empty)");
+        if (sz != 0 && sz != na)
+          per_robot = true;
+      }
+      const double * ptr[5];
+      for (int a = 0; a < 5; a++)
+      {
+        ptr[a] = src[a]->empty() ? nullptr : src[a]->data();
+        if (per_robot && src[a]->size() == na && rows != 1)
+        {
+          keep[a].resize(rows * na);
+          for (size_t i = 0; i < rows; i++)
+            for (size_t k = 0; k < na; k++)
+              keep[a][i * na + k] = (*src[a])[k];
+          ptr[a] = keep[a].data();
+        }
+      }
+      smpc_joint_model_settings m = {ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], per_robot ? 1 : 0, model.stops ? 1 : 0, model.activation, model.stop_erp};
+      return m;
+    }
     static void check(int rc)
     {
       if (rc < 0)

@@ -11,6 +11,7 @@
 #include "smpc_sim_ground_rt.h"
 #include "smpc_sim_ground_env_rt.h"
 #include "smpc_sim_ground_ws_rt.h"
+#include "smpc_sim_ground_joint_rt.h"
 #include "smpc_robot_check.h"
 #include <atomic>
 #include <cstring>
@@ -38,6 +39,8 @@ struct smpc_robot_sim // stand-alone simulator handle: a robot table and nothing
   std::unique_ptr<RobotSimGround> g; // the ground plane, once smpc_robot_sim_set_ground has been called (destroyed before the engine it refers to)
   std::unique_ptr<RobotSimGroundEnv> ge; // its per-robot environment and the staging of the host-buffer solve (destroyed before the ground it refers to)
   std::unique_ptr<RobotSimGroundWs> gw;  // its solver settings, warm buffer and read-outs (destroyed before the ground it refers to)
+  std::unique_ptr<RobotSimGroundJoint> gj; // its joint model and read-outs (destroyed before the ground it refers to)
+  std::vector<double> q_lo, q_hi;        // the robot table's joint limits [nv - 6]: the joint model's defaults
 };
 
 struct smpc_handle
@@ -1220,6 +1223,8 @@ extern "C"
     return guarded([&] {
       std::unique_ptr<smpc_robot_sim> h(new smpc_robot_sim());
       h->e.reset(new RobotSimRt(robot, force_size, batch, gravity, device_id));
+      h->q_lo.assign(robot->q_lo, robot->q_lo + h->e->sz.na);
+      h->q_hi.assign(robot->q_hi, robot->q_hi + h->e->sz.na);
       *out = h.release();
     });
   }
@@ -1302,6 +1307,7 @@ extern "C"
       std::unique_ptr<RobotSimGround> g(new RobotSimGround(*sim->e, settings));
       sim->ge.reset(); // (the per-robot environment and the push go with the ground they were set on)
       sim->gw.reset(); // (and so do the solver settings and the warm buffer)
+      sim->gj.reset(); // (and the joint model)
       sim->g = std::move(g);
     });
   }
@@ -1321,6 +1327,8 @@ extern "C"
       return fail(SMPC_ERR_INVALID, "smpc_robot_sim_step_ground_device: no ground yet, call smpc_robot_sim_set_ground first");
     if (!(dt > 0.0) || !std::isfinite(dt))
       return fail(SMPC_ERR_INVALID, "dt must be positive");
+    if (sim->gj && sim->gj->active) // (a joint model has been set: sim_ground_joint_rt_body, which reads the environment and the solver settings if there are any)
+      return guarded([&] { sim->gj->step_device(X_device, tau_device, dt, sim->ge.get(), sim->gw.get()); });
     if (sim->gw && sim->gw->active) // (solver settings have been set: sim_ground_ws_rt_body, which reads the environment if there is one)
       return guarded([&] { sim->gw->step_device(X_device, tau_device, dt, sim->ge.get()); });
     if (sim->ge && sim->ge->active) // (a per-robot environment or a push has been set: sim_ground_env_rt_body)
@@ -1528,6 +1536,103 @@ extern "C"
         sim->gw.reset(new RobotSimGroundWs(*sim->g)); // (staging only: the handle's ground steps keep their kernel until the setter is called)
       sim->gw->dynamics(n, X, tau, dt, plane, mu, push, push_joint, sim_ground_ws_resolve(st), lambda0, v_next_out, a_out, lambda_out, lambda_contact_out,
                         gap_out, contact_out, sweeps_out, residual_out);
+    });
+  }
+
+  // ---- effort limits, joint damping, armature and joint-limit stops (smpc_sim_ground_joint_rt.h) ----
+  int smpc_robot_sim_set_joint_model(smpc_robot_sim * sim, const smpc_joint_model_settings * model)
+  {
+    if (!sim || !model)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_set_joint_model: no ground yet, call smpc_robot_sim_set_ground first");
+    // admission before anything else: nothing is allocated, and the previous model stays, for values the model does not admit
+    const std::string why = sim_joint_admission_error(sim->e->B, sim->e->sz.na, sim->q_lo.data(), sim->q_hi.data(), model);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      if (!sim->gj)
+        sim->gj.reset(new RobotSimGroundJoint(*sim->g));
+      sim->gj->set_model(model, sim->q_lo.data(), sim->q_hi.data());
+    });
+  }
+  int smpc_robot_sim_get_joint_last(smpc_robot_sim * sim, double ** tau_applied_device, int32_t ** stop_rows_device, double ** lam_stop_device,
+                                    int32_t ** dropped_device)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_get_joint_last: no ground yet, call smpc_robot_sim_set_ground first");
+    // (null pointers before the setter: a getter allocates nothing)
+    const bool have = sim->gj && sim->gj->active;
+    if (tau_applied_device)
+      *tau_applied_device = have ? sim->gj->tau_applied : nullptr;
+    if (stop_rows_device)
+      *stop_rows_device = have ? sim->gj->rows : nullptr;
+    if (lam_stop_device)
+      *lam_stop_device = have ? sim->gj->lams : nullptr;
+    if (dropped_device)
+      *dropped_device = have ? sim->gj->dropped : nullptr;
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_read_joint_last(smpc_robot_sim * sim, double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_read_joint_last: no ground yet, call smpc_robot_sim_set_ground first");
+    if (!(sim->gj && sim->gj->active)) // (zeros before the setter, without allocating or joining the stream)
+    {
+      const int B = sim->e->B, na = sim->e->sz.na;
+      for (int i = 0; i < B; i++)
+      {
+        for (int k = 0; k < na && tau_applied_out; k++)
+          tau_applied_out[(size_t)i * na + k] = 0.0;
+        for (int r = 0; r < SIM_JOINT_MAX_STOPS; r++)
+        {
+          if (stop_rows_out)
+            stop_rows_out[(size_t)i * SIM_JOINT_MAX_STOPS + r] = 0;
+          if (lam_stop_out)
+            lam_stop_out[(size_t)i * SIM_JOINT_MAX_STOPS + r] = 0.0;
+        }
+        if (dropped_out)
+          dropped_out[i] = 0;
+      }
+      return SMPC_OK;
+    }
+    return guarded([&] { sim->gj->read_last(tau_applied_out, stop_rows_out, lam_stop_out, dropped_out); });
+  }
+  int smpc_robot_sim_ground_joint_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const double * plane, const double * mu,
+                                           const double * push, int push_joint, const smpc_ground_solver_settings * settings, const double * lambda0,
+                                           const smpc_joint_model_settings * model, double * v_next_out, double * a_out, double * lambda_out,
+                                           double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out, double * residual_out,
+                                           double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out)
+  {
+    if (!sim || !X || !tau)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_ground_joint_dynamics: no ground yet, call smpc_robot_sim_set_ground first");
+    if (n < 1)
+      return fail(SMPC_ERR_INVALID, "n must be positive");
+    if (!(dt > 0.0) || !std::isfinite(dt))
+      return fail(SMPC_ERR_INVALID, "dt must be positive");
+    const smpc_ground_solver_settings inert = {0, 0.0, 0};
+    const smpc_ground_solver_settings * st = settings ? settings : &inert;
+    std::string why = sim_ground_ws_admission_error(sim->g->gs.sweeps, st);
+    if (why.empty())
+      why = sim_ground_env_admission_error(n, plane, mu);
+    if (why.empty())
+      why = sim_ground_push_admission_error(n, sim->e->sz.nq - 6, push_joint, push);
+    if (why.empty())
+      why = sim_joint_admission_error(n, sim->e->sz.na, sim->q_lo.data(), sim->q_hi.data(), model);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      if (!sim->gj)
+        sim->gj.reset(new RobotSimGroundJoint(*sim->g)); // (staging only: the handle's ground steps keep their kernel until the setter is called)
+      sim->gj->dynamics(n, X, tau, dt, plane, mu, push, push_joint, sim_ground_ws_resolve(st), lambda0, model, sim->q_lo.data(), sim->q_hi.data(),
+                        v_next_out, a_out, lambda_out, lambda_contact_out, gap_out, contact_out, sweeps_out, residual_out, tau_applied_out, stop_rows_out,
+                        lam_stop_out, dropped_out);
     });
   }
 }

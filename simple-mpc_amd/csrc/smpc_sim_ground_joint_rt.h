@@ -1,0 +1,870 @@
+// smpc_sim_ground_joint_rt.h -- the ground of smpc_sim_ground_ws_rt.h with a JOINT MODEL: effort limits, implicit viscous damping,
+// armature and joint-limit stops per robot (DESIGN 3.26 states the model word for word).  sim_ground_joint_rt_body is a sibling of
+// sim_ground_ws_rt_body, which stays as it is: one wavefront per robot, one launch per step, the same phases with these additions
+//   phase 0   the five joint arrays beside the torques, on the lanes that load the torques: tau is clipped to [-tau_max, tau_max] as it
+//             is loaded (a NaN passes through), d, r_a + dt d, q_lo and q_hi go to LDS (null arrays: +inf, 0, 0, no limits)
+//   inertia   Mh = M + diag(0_6, r_a + dt d) as M is formed; one lane walks the actuated joints in ascending order and lists the first
+//             NJ = 8 stop candidates (joint, side, gap term), the rest are counted in `dropped`
+//   phase 3   a stop row is a row of J behind the contact rows with the single entry s at column 6 + k
+//   phase 4   the right-hand side loses d o v_joint; W, G, c0 and 1 / (dt G_rr) cover the stop rows as they cover the contact rows
+//   phase 5   after the contact points of a sweep, the stop rows in ascending order on lane 0 (the update of a normal row); the dot
+//             products of every row run over the whole row of the instantiation, so a stop and a foot see each other; rho takes the stop
+//             rows too.  Stop rows start from exactly 0; the warm row holds contact rows only
+//   phase 7   tau_applied, stop_rows, lam_stop and dropped with the other global stores
+// NROWS counts contact rows AND stop rows: <24> serves up to 12 contact rows (5 points fit), <32> up to 24, each with 8 stop rows.
+// With tau_max = +inf, d = r_a = 0 and stops = 0 every added term is an exact zero and the results equal the sibling's bit for bit.
+// LDS: IdQuantRtScratch (19 024 B) + SimGroundJointLds<NROWS> = SimGroundWsLds<NROWS> + 4 (nv_max - 6) + 8 doubles + 18 ints.
+#pragma once
+#include "smpc_sim_ground_ws_rt.h"
+#include "smpc_sim_joint_dims.h"
+#include <vector>
+
+namespace smpc
+{
+  struct SimGroundJointArgs
+  {
+    SimGroundWsArgs w;      // (sweeps_out / resid_out may be null here)
+    const double * tau_max;  // [na] or [n][na] (device), or null: +inf
+    const double * damping;  // or null: 0
+    const double * armature; // or null: 0
+    const double * q_lo;     // or null: -inf
+    const double * q_hi;     // or null: +inf
+    int per_robot, stops;
+    double activation, stop_erp;
+    double * tau_out;  // [n][na] or null
+    int * rows_out;    // [n][NJ] or null
+    double * lams_out; // [n][NJ] or null
+    int * dropped_out; // [n] or null
+  };
+
+  template <int NROWS>
+  struct SimGroundJointLds
+  {
+    static constexpr int NA = SIM_RT_MAX_NV - 6, NJ = SIM_JOINT_MAX_STOPS;
+    SimGroundWsLds<NROWS> w;
+    double dmp[NA], rad[NA], qlo[NA], qhi[NA]; // d, r_a + dt d, limits
+    double sg[NJ];                             // g / dt or stop_erp g / dt of a stop row
+    int sk[NJ], ss[NJ];                        // its joint and its side (+1 lower, -1 upper)
+    int cnt[2];                                // rows, dropped
+  };
+  static_assert(sizeof(IdQuantRtScratch) + sizeof(SimGroundJointLds<24>) <= 163840 / 3, "three blocks per compute unit");
+  static_assert(sizeof(IdQuantRtScratch) + sizeof(SimGroundJointLds<32>) <= 163840 / 2, "two blocks per compute unit");
+
+  // grid = n, 64 lanes
+  template <int NROWS>
+  SMPC_DEV void sim_ground_joint_rt_body(const SimGroundJointArgs & ja, int block)
+  {
+    typedef IdQuantRtScratch SC;
+    typedef SimGroundLds<NROWS> L;
+    typedef SimGroundEnvLds<NROWS> LE;
+    typedef SimGroundWsLds<NROWS> LW;
+    typedef SimGroundJointLds<NROWS> LJ;
+    constexpr int NT = 64, MAXJ = SC::MAXJ, NF = SC::NF, LDM = L::NV, NCM = L::NC, NR = L::NR, LDG = L::LDG, NE = SIM_GROUND_ENV_DOUBLES, NJ = LJ::NJ,
+                  NPM = (NROWS - NJ) / 3;
+    static_assert(LDM <= NT - NE - 1 && NR <= NT && NCM <= 32 && NPM >= 1 && NPM <= L::NP && 3 * NPM + NJ <= NCM && NPM <= 24 && LDM - 6 <= LJ::NA,
+                  "torques and environment load side by side; rows on lanes 32 .. 63; points on lanes 32 .. 55");
+    const SimGroundWsArgs & wa = ja.w;
+    const SimGroundEnvArgs & ea = wa.e;
+    const SimGroundArgs & ka = ea.g;
+    const int inst = block;
+    const IdRtDevModel & mi = *ka.model;
+    // (wave-uniform sizes from the device table and the arguments, clamped so that no value can index outside the LDS arrays)
+    const int nj = mi.t.njoints < MAXJ ? (mi.t.njoints > 1 ? mi.t.njoints : 1) : MAXJ;
+    const int nv = nj + 5, nq = nj + 6, nx = 2 * nj + 11, na = nv - 6;
+    const int P = ka.P < SIM_GROUND_MAX_PPF ? (ka.P > 1 ? ka.P : 1) : SIM_GROUND_MAX_PPF;
+    const int maxf = NPM / P < NF ? NPM / P : NF;
+    const int nfeet = mi.t.nfeet < maxf ? (mi.t.nfeet > 0 ? mi.t.nfeet : 0) : maxf;
+    const int npts = nfeet * P, nr = 3 * npts;
+    const int jpush = ea.push_joint < nj ? (ea.push_joint > 0 ? ea.push_joint : 0) : nj - 1;
+    const double dt = ka.dt;
+    const bool warm = wa.warm_start != 0 && wa.lam0 != nullptr;
+    SMPC_LDS(SC, scs, 1);
+    SMPC_LDS(LJ, ls, 1);
+    SC & sc = scs[0];
+    LJ & jm = ls[0];
+    LW & w = jm.w;
+    LE & e = w.e;
+    L & s = e.s;
+    // ---- phase 0: every global load (the state and the joint constants: first phase of rt_tree_phases) ----
+    SMPC_LANES(NT)
+    {
+      if (lane < LDM)
+      {
+        double t = 0.0;
+        if (lane >= 6 && lane < nv)
+        {
+          const int k = lane - 6;
+          const size_t at = (ja.per_robot != 0 ? (size_t)inst * na : (size_t)0) + k;
+          t = ka.tau[(size_t)inst * na + k];
+          const double tm = ja.tau_max != nullptr ? ja.tau_max[at] : INFINITY;
+          const double d = ja.damping != nullptr ? ja.damping[at] : 0.0;
+          const double ra = ja.armature != nullptr ? ja.armature[at] : 0.0;
+          t = t > tm ? tm : (t < -tm ? -tm : t); // (a NaN passes through)
+          jm.dmp[k] = d;
+          jm.rad[k] = ra + dt * d;
+          jm.qlo[k] = ja.q_lo != nullptr ? ja.q_lo[at] : -INFINITY;
+          jm.qhi[k] = ja.q_hi != nullptr ? ja.q_hi[at] : INFINITY;
+        }
+        s.tau[lane] = t;
+      }
+      if (lane >= NT - NE)
+      {
+        const int k = lane - (NT - NE);
+        double val;
+        if (k < 4)
+          val = ea.plane != nullptr ? ea.plane[(size_t)inst * 4 + k] : (k == 2 ? 1.0 : (k == 3 ? ka.ground_z : 0.0));
+        else if (k == 4)
+          val = ea.mu != nullptr ? ea.mu[inst] : ka.mu;
+        else
+          val = ea.push != nullptr ? ea.push[(size_t)inst * 6 + k - 5] : 0.0;
+        e.env[k] = val;
+      }
+      if (lane < NCM) // the start vector: the robot's warm row (contact rows only), an entry that is not finite reads as exactly 0
+      {
+        double val = 0.0;
+        if (warm && lane < nr)
+        {
+          const double v = wa.lam0[(size_t)inst * nr + lane];
+          val = fabs(v) <= 1.7976931348623157e308 ? v : 0.0;
+        }
+        s.lam[lane] = val;
+      }
+    }
+    SMPC_LANES_END_WAVE
+    // ---- phases 1, 2 ----
+    rt_tree_phases(sc, mi, ka.X + (size_t)inst * nx, mk3(ka.gravity[0], ka.gravity[1], ka.gravity[2]));
+    // ---- Mh = M + diag(0_6, r_a + dt d) (both triangles from one expression: symmetric bit for bit); contact points, gaps, frame and push
+    // point; the stop candidates ----
+    SMPC_LANES(NT)
+    {
+      for (int idx = lane; idx < nv * nv; idx += NT)
+      {
+        const int r = idx / nv, c = idx % nv;
+        const int lo = r < c ? r : c, hi = r < c ? c : r;
+        const int jl = lo < 6 ? 0 : lo - 5, jh = hi < 6 ? 0 : hi - 5;
+        double val = ((sc.anc[jh] >> jl) & 1u) ? id_rt_dot6(&sc.S[lo * 6], &sc.F[hi * 6]) : 0.0;
+        if (r == c && r >= 6)
+          val += jm.rad[r - 6];
+        s.M[r * LDM + c] = val;
+      }
+      for (int idx = lane; idx < NCM * LDM; idx += NT)
+        s.J[idx] = 0.0;
+      if (lane < NCM)
+      {
+        s.c0[lane] = 0.0;
+        w.ig[lane][0] = 0.0;
+        w.ig[lane][1] = 0.0;
+      }
+      if (lane >= 32 && lane < 32 + NPM)
+      {
+        const int c = lane - 32;
+        double gap = 0.0;
+        V3 p = mk3(0.0, 0.0, 0.0);
+        if (c < npts)
+        {
+          const int f = c / P, k = c % P, jf = sc.fj[f];
+          p = ld3(&sc.footp[f * 3]) + ldm3(&sc.oR[jf * 9]) * mk3(ka.points[k][0], ka.points[k][1], ka.points[k][2]); // foot frame rotation = joint rotation
+          double acc = e.env[0] * p.x;
+          acc += e.env[1] * p.y;
+          acc += e.env[2] * p.z;
+          gap = acc - e.env[3];
+        }
+        st3(&s.pc[c * 3], p);
+        s.gap[c] = gap;
+      }
+      if (lane == 60) // stop candidates in ascending k: min(g-, g+) < activation; lower if g- <= g+
+      {
+        int rows = 0, dropped = 0;
+        if (ja.stops != 0)
+          for (int k = 0; k < na; k++)
+          {
+            const double q = sc.x[7 + k];
+            const double gm = q - jm.qlo[k], gp = jm.qhi[k] - q;
+            const bool lower = gm <= gp;
+            const double g = lower ? gm : gp;
+            if (g < ja.activation)
+            {
+              if (rows < NJ)
+              {
+                jm.sk[rows] = k;
+                jm.ss[rows] = lower ? 1 : -1;
+                jm.sg[rows] = g >= 0.0 ? g / dt : ja.stop_erp * g / dt;
+                rows++;
+              }
+              else
+                dropped++;
+            }
+          }
+        for (int r = rows; r < NJ; r++)
+        {
+          jm.sk[r] = 0;
+          jm.ss[r] = 0;
+          jm.sg[r] = 0.0;
+        }
+        jm.cnt[0] = rows;
+        jm.cnt[1] = dropped;
+      }
+      if (lane == 62) // t1 = (e_y x n) / |e_y x n|, t2 = n x t1 (sim_ground_env_frame)
+      {
+        const double n0 = e.env[0], n1 = e.env[1], n2 = e.env[2];
+        const double cx = n2, cz = -n0;
+        const double inv = 1.0 / sqrt(cx * cx + cz * cz);
+        const V3 t1 = mk3(cx * inv, 0.0, cz * inv);
+        st3(e.t1, t1);
+        st3(e.t2, mk3(n1 * t1.z - n2 * t1.y, n2 * t1.x - n0 * t1.z, n0 * t1.y - n1 * t1.x));
+      }
+      if (lane == 63) // r = p_j + R_j o and r x f
+      {
+        const V3 r = ld3(&sc.op[jpush * 3]) + ldm3(&sc.oR[jpush * 9]) * ld3(&e.env[8]);
+        st3(e.r, r);
+        st3(e.rxf, cross(r, ld3(&e.env[5])));
+      }
+    }
+    SMPC_LANES_END_WAVE
+    // (wave-uniform: one wavefront owns one robot; clamped before it indexes LDS)
+    const int ns_raw = (int)SMPC_UNIFORM_U32(jm.cnt[0]);
+    const int ns_max = NCM - nr < NJ ? NCM - nr : NJ;
+    const int ns = ns_raw < ns_max ? (ns_raw > 0 ? ns_raw : 0) : ns_max;
+    const int nrt = nr + ns;
+    // ---- phase 3: the rows of every point, t1 t2 n in the contact frame; the stop rows behind them ----
+    SMPC_LANES(NT)
+    {
+      for (int idx = lane; idx < npts * nv; idx += NT)
+      {
+        const int c = idx / nv, k = idx % nv;
+        const int jf = sc.fj[c / P], jk = k < 6 ? 0 : k - 5;
+        if ((sc.anc[jf] >> jk) & 1u)
+        {
+          const SV Sk = ldsv(&sc.S[k * 6]);
+          const V3 lin = Sk.l + cross(Sk.a, ld3(&s.pc[c * 3])); // velocity of the point under the unit twist of column k
+          double r0 = e.t1[0] * lin.x;
+          r0 += e.t1[1] * lin.y;
+          r0 += e.t1[2] * lin.z;
+          double r1 = e.t2[0] * lin.x;
+          r1 += e.t2[1] * lin.y;
+          r1 += e.t2[2] * lin.z;
+          double r2 = e.env[0] * lin.x;
+          r2 += e.env[1] * lin.y;
+          r2 += e.env[2] * lin.z;
+          s.J[(3 * c + 0) * LDM + k] = r0;
+          s.J[(3 * c + 1) * LDM + k] = r1;
+          s.J[(3 * c + 2) * LDM + k] = r2;
+        }
+      }
+      if (lane >= 32 && lane < 32 + ns) // (other lanes than the ones that write the rows of the points: J_r = s e_{6 + k})
+      {
+        const int r = lane - 32;
+        const int k = jm.sk[r] < na ? (jm.sk[r] > 0 ? jm.sk[r] : 0) : na - 1;
+        s.J[(nr + r) * LDM + 6 + k] = (double)jm.ss[r];
+      }
+    }
+    SMPC_LANES_END_WAVE
+    // ---- phase 4: Mh = L L^T ; W = Mh^-1 [S tc - h - d o v + Q | J^T] ----
+    SMPC_LANES(NT)
+    for (int idx = lane; idx < nv * NR; idx += NT)
+    {
+      const int k = idx / NR, c = idx % NR;
+      double val;
+      if (c == 0)
+      {
+        double q = 0.0;
+        if ((sc.anc[jpush] >> (k < 6 ? 0 : k - 5)) & 1u)
+        {
+          const SV Sk = ldsv(&sc.S[k * 6]);
+          q = Sk.l.x * e.env[5];
+          q += Sk.l.y * e.env[6];
+          q += Sk.l.z * e.env[7];
+          q += Sk.a.x * e.rxf[0];
+          q += Sk.a.y * e.rxf[1];
+          q += Sk.a.z * e.rxf[2];
+        }
+        val = s.tau[k] - sc.h[k];
+        if (k >= 6)
+          val -= jm.dmp[k - 6] * sc.x[nq + k];
+        val += q;
+      }
+      else
+        val = s.J[(c - 1) * LDM + k];
+      s.W[idx] = val;
+    }
+    SMPC_LANES_END_WAVE
+    rt_wave_cholesky(s.M, LDM, nv, s.tmp);
+    rt_wave_chol_solve<NR>(s.M, LDM, nv, s.W, NR, s.row);
+    // free velocity
+    SMPC_LANES(NT)
+    if (lane < nv)
+      s.vf[lane] = sc.x[nq + lane] + dt * s.W[lane * NR];
+    SMPC_LANES_END_WAVE
+    // Delassus matrix with the compliance on its diagonal, c0 = J v_f + the gap term on the normal rows and on the stop rows
+    SMPC_LANES(NT)
+    {
+      for (int idx = lane; idx < NCM * NCM; idx += NT)
+      {
+        const int c = idx / NCM, d = idx % NCM;
+        double acc = 0.0;
+        if (c < nrt && d < nrt) // (zero beyond the robot's rows: the sweep runs over the whole row)
+        {
+          for (int k = 0; k < nv; k++)
+            acc += s.J[c * LDM + k] * s.W[k * NR + 1 + d];
+          if (c == d)
+            acc += ka.compliance;
+        }
+        s.G[c * LDG + d] = acc;
+      }
+      if (lane >= 32 && lane < 32 + nrt)
+      {
+        const int r = lane - 32;
+        double acc = 0.0;
+        if (r < nr)
+        {
+          for (int k = 0; k < nv; k++)
+            acc += s.J[r * LDM + k] * s.vf[k];
+          if (r % 3 == 2)
+          {
+            const double phi = s.gap[r / 3];
+            acc += phi >= 0.0 ? phi / dt : ka.erp * phi / dt;
+          }
+        }
+        else
+        {
+          const int i = r - nr;
+          const int k = jm.sk[i] < na ? (jm.sk[i] > 0 ? jm.sk[i] : 0) : na - 1;
+          acc = (double)jm.ss[i] * s.vf[6 + k] + jm.sg[i];
+        }
+        s.c0[r] = acc;
+      }
+    }
+    SMPC_LANES_END_WAVE
+    SMPC_LANES(NT)
+    if (lane < nrt)
+    {
+      const double dg = dt * s.G[lane * LDG + lane];
+      w.ig[lane][0] = 1.0 / dg;
+      w.ig[lane][1] = dg;
+    }
+    SMPC_LANES_END_WAVE
+    // ---- phase 5: projected Gauss-Seidel from the start vector: the points in ascending order (the sweep of sim_ground_ws_rt_body), then
+    // the stop rows in ascending order; at most `sweeps` sweeps; rho of a sweep on lanes 0 and 1, the stopping test once per sweep ----
+    const int min_sweeps = wa.min_sweeps > 1 ? wa.min_sweeps : 1;
+    const bool stopping = wa.tol > 0.0;
+    int used = 0;
+    double rho = 0.0;
+    SMPC_PL(double, rmax, NT);
+    SMPC_PL(double, tdg, NT); // dt G_rr of the lane's tangential row, from the phase of the candidates to the projection
+    SMPC_LANES(NT)
+    {
+      SMPC_PLV(rmax) = 0.0;
+      SMPC_PLV(tdg) = 0.0;
+    }
+    SMPC_LANES_END_WAVE
+    for (int sw = 0; sw < ka.sweeps; sw++)
+    {
+      for (int c = 0; c < npts; c++)
+      {
+        const int rn = 3 * c + 2;
+        SMPC_LANES(NT)
+        if (lane == 0)
+        {
+          double acc = 0.0;
+#pragma unroll
+          for (int j = 0; j < NCM; j++) // (compile-time bound: the loads of the row are issued ahead of the chain of multiply-adds)
+            acc += s.G[rn * LDG + j] * s.lam[j];
+          const double old = s.lam[rn];
+          const double idg = w.ig[rn][0], dg = w.ig[rn][1];
+          const double val = fmax(0.0, old - (s.c0[rn] + dt * acc) * idg);
+          s.lam[rn] = val;
+          SMPC_PLV(rmax) = sim_ground_ws_max(SMPC_PLV(rmax), fabs(val - old) * dg);
+        }
+        SMPC_LANES_END_WAVE
+        // both tangential candidates from the same lambda, the one that already holds the new normal force
+        SMPC_LANES(NT)
+        if (lane < 2)
+        {
+          const int rt = 3 * c + lane;
+          double acc = 0.0;
+#pragma unroll
+          for (int j = 0; j < NCM; j++)
+            acc += s.G[rt * LDG + j] * s.lam[j];
+          const double idg = w.ig[rt][0];
+          SMPC_PLV(tdg) = w.ig[rt][1];
+          s.tc[lane] = s.lam[rt] - (s.c0[rt] + dt * acc) * idg;
+        }
+        SMPC_LANES_END_WAVE
+        SMPC_LANES(NT)
+        if (lane < 2)
+        {
+          const int rt = 3 * c + lane;
+          const double t1 = s.tc[0], t2 = s.tc[1];
+          const double nrm = sqrt(t1 * t1 + t2 * t2), lim = e.env[4] * s.lam[rn];
+          const double old = s.lam[rt];
+          double t = s.tc[lane];
+          if (nrm > lim)
+            t = t * (lim / nrm);
+          if (nrm == 0.0)
+            t = 0.0;
+          s.lam[rt] = t;
+          SMPC_PLV(rmax) = sim_ground_ws_max(SMPC_PLV(rmax), fabs(t - old) * SMPC_PLV(tdg));
+        }
+        SMPC_LANES_END_WAVE
+      }
+      for (int r = nr; r < nrt; r++) // the stop rows: the update of a normal row
+      {
+        SMPC_LANES(NT)
+        if (lane == 0)
+        {
+          double acc = 0.0;
+#pragma unroll
+          for (int j = 0; j < NCM; j++)
+            acc += s.G[r * LDG + j] * s.lam[j];
+          const double old = s.lam[r];
+          const double idg = w.ig[r][0], dg = w.ig[r][1];
+          const double val = fmax(0.0, old - (s.c0[r] + dt * acc) * idg);
+          s.lam[r] = val;
+          SMPC_PLV(rmax) = sim_ground_ws_max(SMPC_PLV(rmax), fabs(val - old) * dg);
+        }
+        SMPC_LANES_END_WAVE
+      }
+      SMPC_LANES(NT)
+      if (lane < 2)
+      {
+        w.rho[lane] = SMPC_PLV(rmax);
+        SMPC_PLV(rmax) = 0.0; // (the next sweep's maximum starts at 0)
+      }
+      SMPC_LANES_END_WAVE
+      // (the whole wave reads the two maxima back: after the lanes' end-of-wave point, so that the sequential test backend sees both)
+      rho = sim_ground_ws_max(w.rho[0], w.rho[1]);
+      used = sw + 1;
+      if (SMPC_UNIFORM_U32(stopping && used >= min_sweeps && rho <= wa.tol ? 1u : 0u) != 0u)
+        break;
+    }
+    // ---- phase 6: a = W_0 + W_1 lambda ; v+ = v_f + dt W_1 lambda ; q+ = q (+) v+ dt ----
+    SMPC_LANES(NT)
+    if (lane < nv)
+    {
+      double acc = 0.0;
+      for (int c = 0; c < nrt; c++)
+        acc += s.W[lane * NR + 1 + c] * s.lam[c];
+      s.a[lane] = s.W[lane * NR] + acc;
+      const double vn = s.vf[lane] + dt * acc;
+      s.xn[nq + lane] = vn;
+      s.dx[lane] = vn * dt;
+    }
+    SMPC_LANES_END_WAVE
+    const bool step = ka.advance != 0;
+    if (step)
+    {
+      SMPC_LANES(NT)
+      if (lane == 0)
+      {
+        const double * x = sc.x;
+        const V3 dv = ld3(s.dx), dw = ld3(s.dx + 3);
+        const M3 R0 = quat_to_R(Quat{x[3], x[4], x[5], x[6]});
+        const SE3 E = exp6(dv, dw);
+        st3(s.xn, ld3(x) + R0 * E.p);
+        Quat qn = quat_mul(Quat{x[3], x[4], x[5], x[6]}, quat_exp(dw));
+        const double n = 1.0 / sqrt(qn.x * qn.x + qn.y * qn.y + qn.z * qn.z + qn.w * qn.w);
+        s.xn[3] = qn.x * n;
+        s.xn[4] = qn.y * n;
+        s.xn[5] = qn.z * n;
+        s.xn[6] = qn.w * n;
+      }
+      else if (lane >= 6 && lane < nv)
+        s.xn[lane + 1] = sc.x[lane + 1] + s.dx[lane];
+      SMPC_LANES_END_WAVE
+    }
+    // ---- phase 7: every global store; the forces in world axes, lambda_world(c) = Rc lambda_c, and in the contact frame ----
+    SMPC_LANES(NT)
+    {
+      if (step)
+        for (int i = lane; i < nx; i += NT)
+          ka.X[(size_t)inst * nx + i] = s.xn[i];
+      if (lane < nv)
+      {
+        ka.a_out[(size_t)inst * nv + lane] = s.a[lane];
+        if (ka.vnext_out != nullptr)
+          ka.vnext_out[(size_t)inst * nv + lane] = s.xn[nq + lane];
+      }
+      if (lane < na && ja.tau_out != nullptr)
+        ja.tau_out[(size_t)inst * na + lane] = s.tau[6 + lane];
+      if (lane < nr)
+      {
+        const int c = lane / 3, i = lane % 3;
+        double wl = e.t1[i] * s.lam[3 * c];
+        wl += e.t2[i] * s.lam[3 * c + 1];
+        wl += e.env[i] * s.lam[3 * c + 2];
+        ka.lam_out[(size_t)inst * nr + lane] = wl;
+        if (wa.lamc_out != nullptr)
+          wa.lamc_out[(size_t)inst * nr + lane] = s.lam[lane];
+      }
+      if (lane < npts && ka.gap_out != nullptr)
+        ka.gap_out[(size_t)inst * npts + lane] = s.gap[lane];
+      if (lane >= 32 && lane < 32 + NJ)
+      {
+        const int r = lane - 32;
+        if (ja.rows_out != nullptr)
+          ja.rows_out[(size_t)inst * NJ + r] = r < ns ? jm.ss[r] * (jm.sk[r] + 1) : 0;
+        if (ja.lams_out != nullptr)
+          ja.lams_out[(size_t)inst * NJ + r] = r < ns ? s.lam[nr + r] : 0.0;
+      }
+      if (lane == 0)
+      {
+        unsigned word = 0u;
+        for (int c = 0; c < npts; c++)
+          if (s.lam[3 * c + 2] > 0.0)
+            word |= 1u << c;
+        ka.contact_out[inst] = word;
+      }
+      if (lane == 1)
+      {
+        if (wa.sweeps_out != nullptr)
+          wa.sweeps_out[inst] = used;
+        if (wa.resid_out != nullptr)
+          wa.resid_out[inst] = rho;
+      }
+      if (lane == 2 && ja.dropped_out != nullptr)
+        ja.dropped_out[inst] = jm.cnt[1] + (ns_raw > ns ? ns_raw - ns : 0);
+    }
+    SMPC_LANES_END_WAVE
+  }
+
+  // ---- host: the joint model and the per-robot read-outs of one simulator handle's ground (a sibling of RobotSimGroundWs; the
+  // environment and the solver state of a step are handed in by the caller).  `active` once the setter has been called: from then on the
+  // handle's ground steps launch the kernel above.  The host-buffer solve needs no setter, allocates its staging only and never touches the
+  // handle's buffers. ----
+  struct RobotSimGroundJoint
+  {
+    RobotSimGround & g;
+    bool active = false;
+    SimJointScalars sc{0, SIM_JOINT_DEFAULT_ACTIVATION, SIM_JOINT_DEFAULT_STOP_ERP};
+    // the model, always [B][na] on the device; tau_max / damping / armature are handed to the kernel only if they were given
+    double *tmax = nullptr, *dmp = nullptr, *arm = nullptr, *qlo = nullptr, *qhi = nullptr;
+    bool have_tmax = false, have_dmp = false, have_arm = false;
+    double * tau_applied = nullptr; // [B][na]
+    int * rows = nullptr;           // [B][NJ]
+    double * lams = nullptr;        // [B][NJ]
+    int * dropped = nullptr;        // [B]
+    // host-buffer form (n states, n need not be B): grown on demand
+    int cap = 0;
+    std::vector<void *> staging;
+    double *hX = nullptr, *hTau = nullptr, *hV = nullptr, *hA = nullptr, *hLam = nullptr, *hLamC = nullptr, *hLam0 = nullptr, *hGap = nullptr, *hEnv = nullptr,
+           *hRes = nullptr, *hModel = nullptr, *hTauA = nullptr, *hLamS = nullptr;
+    unsigned * hCon = nullptr;
+    int *hSw = nullptr, *hRows = nullptr, *hDrop = nullptr;
+
+    // (nothing is allocated here: the host-buffer solve needs the staging only; the handle-owned arrays come with the first set_model)
+    explicit RobotSimGroundJoint(RobotSimGround & ground) : g(ground) {}
+    void allocate()
+    {
+      if (tau_applied != nullptr)
+        return;
+      RobotSimRt & sim = g.sim;
+      const SimJointSizes z = sim_joint_sizes(sim.B, sim.sz.na);
+      AllocScope scope; // (a failing allocation below releases the ones before it, and the pointers are kept only once all have succeeded)
+      double * n_tmax = (double *)dev_alloc(z.array_bytes);
+      double * n_dmp = (double *)dev_alloc(z.array_bytes);
+      double * n_arm = (double *)dev_alloc(z.array_bytes);
+      double * n_qlo = (double *)dev_alloc(z.array_bytes);
+      double * n_qhi = (double *)dev_alloc(z.array_bytes);
+      double * n_tau = (double *)dev_alloc(z.tau_bytes);
+      int * n_rows = (int *)dev_alloc(z.rows_bytes);
+      double * n_lams = (double *)dev_alloc(z.lam_bytes);
+      int * n_dropped = (int *)dev_alloc(z.dropped_bytes);
+      scope.commit();
+      tmax = n_tmax;
+      dmp = n_dmp;
+      arm = n_arm;
+      qlo = n_qlo;
+      qhi = n_qhi;
+      tau_applied = n_tau;
+      rows = n_rows;
+      lams = n_lams;
+      dropped = n_dropped;
+    }
+    RobotSimGroundJoint(const RobotSimGroundJoint &) = delete;
+    RobotSimGroundJoint & operator=(const RobotSimGroundJoint &) = delete;
+    void zero_outputs()
+    {
+      RobotSimRt & sim = g.sim;
+      const SimJointSizes z = sim_joint_sizes(sim.B, sim.sz.na);
+      dev_zero(tau_applied, z.tau_bytes, sim.stream);
+      dev_zero(rows, z.rows_bytes, sim.stream);
+      dev_zero(lams, z.lam_bytes, sim.stream);
+      dev_zero(dropped, z.dropped_bytes, sim.stream);
+      stream_sync(sim.stream);
+    }
+    void free_staging()
+    {
+      for (void * p : staging)
+        dev_free(p);
+      staging.clear();
+      hX = hTau = hV = hA = hLam = hLamC = hLam0 = hGap = hEnv = hRes = hModel = hTauA = hLamS = nullptr;
+      hCon = nullptr;
+      hSw = hRows = hDrop = nullptr;
+      cap = 0;
+    }
+    ~RobotSimGroundJoint()
+    {
+      free_staging();
+      dev_free(tmax);
+      dev_free(dmp);
+      dev_free(arm);
+      dev_free(qlo);
+      dev_free(qhi);
+      dev_free(tau_applied);
+      dev_free(rows);
+      dev_free(lams);
+      dev_free(dropped);
+    }
+    // (the caller has run sim_joint_admission_error) copies the model to the device, a row per robot, and zeroes the read-outs
+    void set_model(const smpc_joint_model_settings * m, const double * tab_lo, const double * tab_hi)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      const int B = sim.B, na = sim.sz.na;
+      const size_t bytes = sim_joint_sizes(B, na).array_bytes;
+      sim.wait(); // (a step in flight still reads the arrays that are replaced below)
+      allocate();
+      std::vector<double> h((size_t)B * na);
+      auto put = [&](double * dst, const double * src, const double * fallback) {
+        for (int i = 0; i < B; i++)
+          for (int k = 0; k < na; k++)
+            h[(size_t)i * na + k] = src ? src[(m->per_robot ? (size_t)i * na : (size_t)0) + k] : fallback[k];
+        h2d(dst, h.data(), bytes, sim.stream);
+        stream_sync(sim.stream); // (`h` is refilled for the next array)
+      };
+      if (m->tau_max)
+        put(tmax, m->tau_max, nullptr);
+      if (m->damping)
+        put(dmp, m->damping, nullptr);
+      if (m->armature)
+        put(arm, m->armature, nullptr);
+      put(qlo, m->q_lo, tab_lo);
+      put(qhi, m->q_hi, tab_hi);
+      have_tmax = m->tau_max != nullptr;
+      have_dmp = m->damping != nullptr;
+      have_arm = m->armature != nullptr;
+      zero_outputs();
+      sc = sim_joint_resolve(m);
+      active = true;
+    }
+    void run(int n, const SimGroundJointArgs & ja)
+    {
+      if (g.gz.inst == 12)
+        launch<SimGroundJointArgs, sim_ground_joint_rt_body<24>, 64, 1, 0>(n, g.sim.stream, ja);
+      else
+        launch<SimGroundJointArgs, sim_ground_joint_rt_body<32>, 64, 1, 0>(n, g.sim.stream, ja);
+    }
+    // `env` and `ws` may be null or inactive: the handle's uniform ground, no push; `sweeps` sweeps from zero
+    void step_device(double * X_dev, const double * tau_dev, double dt, const RobotSimGroundEnv * env, RobotSimGroundWs * ws)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      SimGroundJointArgs ja;
+      SimGroundWsArgs & wa = ja.w;
+      wa.e.g = g.args(dt);
+      wa.e.g.X = X_dev;
+      wa.e.g.tau = tau_dev;
+      wa.e.g.advance = 1;
+      wa.e.g.a_out = sim.a;
+      wa.e.g.lam_out = g.lam;
+      wa.e.g.contact_out = g.contact;
+      const bool have = env != nullptr && env->active;
+      wa.e.plane = have ? env->plane : nullptr;
+      wa.e.mu = have ? env->mu : nullptr;
+      wa.e.push = have ? env->push : nullptr;
+      wa.e.push_joint = have ? env->push_joint : 0;
+      const bool solver = ws != nullptr && ws->active;
+      wa.lam0 = solver ? ws->warm : nullptr;
+      wa.lamc_out = solver ? ws->warm : nullptr;
+      wa.sweeps_out = solver ? ws->sweeps : nullptr;
+      wa.resid_out = solver ? ws->resid : nullptr;
+      wa.warm_start = solver ? ws->ws.warm_start : 0;
+      wa.min_sweeps = solver ? ws->ws.min_sweeps : 1;
+      wa.tol = solver ? ws->ws.tol : 0.0;
+      ja.tau_max = have_tmax ? tmax : nullptr;
+      ja.damping = have_dmp ? dmp : nullptr;
+      ja.armature = have_arm ? arm : nullptr;
+      ja.q_lo = qlo;
+      ja.q_hi = qhi;
+      ja.per_robot = 1;
+      ja.stops = sc.stops;
+      ja.activation = sc.activation;
+      ja.stop_erp = sc.stop_erp;
+      ja.tau_out = tau_applied;
+      ja.rows_out = rows;
+      ja.lams_out = lams;
+      ja.dropped_out = dropped;
+      run(sim.B, ja);
+    }
+    void read_last(double * tau_out, int * rows_out, double * lams_out, int * dropped_out)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      const SimJointSizes z = sim_joint_sizes(sim.B, sim.sz.na);
+      if (tau_out)
+        d2h(tau_out, tau_applied, z.tau_bytes, sim.stream);
+      if (rows_out)
+        d2h(rows_out, rows, z.rows_bytes, sim.stream);
+      if (lams_out)
+        d2h(lams_out, lams, z.lam_bytes, sim.stream);
+      if (dropped_out)
+        d2h(dropped_out, dropped, z.dropped_bytes, sim.stream);
+      stream_sync(sim.stream);
+    }
+    template <class T>
+    T * stage(size_t count)
+    {
+      staging.push_back(nullptr); // (the slot first: a failing push_back after the allocation would lose the pointer)
+      T * p = (T *)dev_alloc(count * sizeof(T));
+      staging.back() = p;
+      return p;
+    }
+    // (the caller has run the admissions) `m` may be null: the inert model
+    void dynamics(int n, const double * X, const double * tau, double dt, const double * plane_h, const double * mu_h, const double * push_h, int joint,
+                  const SimGroundWsSettings & st, const double * lam0_h, const smpc_joint_model_settings * m, const double * tab_lo, const double * tab_hi,
+                  double * v_out, double * a_out, double * lam_out, double * lamc_out, double * gap_out, unsigned * con_out, int * sweeps_out, double * resid_out,
+                  double * tau_applied_out, int * rows_out, double * lams_out, int * dropped_out)
+    {
+      if (n < 1)
+        throw InvalidCall("n must be positive");
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      const SimRtSizes & sz = sim.sz;
+      const SimGroundSizes & gz = g.gz;
+      stream_t stream = sim.stream;
+      constexpr int NE = SIM_GROUND_ENV_DOUBLES, NJ = SIM_JOINT_MAX_STOPS;
+      const int na = sz.na;
+      if (n > cap)
+      {
+        stream_sync(stream);
+        free_staging();
+        try
+        {
+          hX = stage<double>((size_t)n * sz.nx);
+          hTau = stage<double>((size_t)n * na);
+          hV = stage<double>((size_t)n * sz.nv);
+          hA = stage<double>((size_t)n * sz.nv);
+          hLam = stage<double>((size_t)n * gz.nrows);
+          hLamC = stage<double>((size_t)n * gz.nrows);
+          hLam0 = stage<double>((size_t)n * gz.nrows);
+          hGap = stage<double>((size_t)n * gz.npts);
+          hEnv = stage<double>((size_t)n * NE); // planes [n][4] | mu [n] | pushes [n][6]
+          hRes = stage<double>((size_t)n);
+          hModel = stage<double>((size_t)5 * n * na); // tau_max | damping | armature | q_lo | q_hi, [n][na] each
+          hTauA = stage<double>((size_t)n * na);
+          hLamS = stage<double>((size_t)n * NJ);
+          hCon = stage<unsigned>((size_t)n);
+          hSw = stage<int>((size_t)n);
+          hRows = stage<int>((size_t)n * NJ);
+          hDrop = stage<int>((size_t)n);
+        }
+        catch (...)
+        {
+          free_staging();
+          throw;
+        }
+        cap = n;
+      }
+      double *dPlane = hEnv, *dMu = hEnv + (size_t)cap * 4, *dPush = hEnv + (size_t)cap * 5;
+      h2d(hX, X, (size_t)n * sz.nx * sizeof(double), stream);
+      h2d(hTau, tau, (size_t)n * na * sizeof(double), stream);
+      if (plane_h)
+        h2d(dPlane, plane_h, (size_t)n * 4 * sizeof(double), stream);
+      if (mu_h)
+        h2d(dMu, mu_h, (size_t)n * sizeof(double), stream);
+      if (push_h)
+        h2d(dPush, push_h, (size_t)n * 6 * sizeof(double), stream);
+      const bool start = st.warm_start != 0 && lam0_h != nullptr;
+      if (start)
+        h2d(hLam0, lam0_h, (size_t)n * gz.nrows * sizeof(double), stream);
+      const int per_robot = m && m->per_robot ? 1 : 0;
+      const size_t count = (size_t)(per_robot ? n : 1) * na;
+      const double * src[5] = {m ? m->tau_max : nullptr, m ? m->damping : nullptr, m ? m->armature : nullptr, m && m->q_lo ? m->q_lo : tab_lo,
+                               m && m->q_hi ? m->q_hi : tab_hi};
+      // (a table row beside per-robot rows: every array of a launch has one stride, so the table's limits are repeated per robot)
+      std::vector<double> rep;
+      const double * dev[5];
+      for (int a = 0; a < 5; a++)
+      {
+        double * dst = hModel + (size_t)a * cap * na;
+        dev[a] = src[a] ? dst : nullptr;
+        if (!src[a])
+          continue;
+        const bool table = a >= 3 && !(m && (a == 3 ? m->q_lo : m->q_hi));
+        if (table && per_robot)
+        {
+          rep.resize((size_t)n * na);
+          for (int i = 0; i < n; i++)
+            for (int k = 0; k < na; k++)
+              rep[(size_t)i * na + k] = src[a][k];
+          h2d(dst, rep.data(), rep.size() * sizeof(double), stream);
+          stream_sync(stream); // (`rep` is refilled for the next array)
+        }
+        else
+          h2d(dst, src[a], count * sizeof(double), stream);
+      }
+      const SimJointScalars js = sim_joint_resolve(m);
+      SimGroundJointArgs ja;
+      SimGroundWsArgs & wa = ja.w;
+      wa.e.g = g.args(dt);
+      wa.e.g.X = hX;
+      wa.e.g.tau = hTau;
+      wa.e.g.advance = 0;
+      wa.e.g.a_out = hA;
+      wa.e.g.lam_out = hLam;
+      wa.e.g.contact_out = hCon;
+      wa.e.g.vnext_out = hV;
+      wa.e.g.gap_out = hGap;
+      wa.e.plane = plane_h ? dPlane : nullptr;
+      wa.e.mu = mu_h ? dMu : nullptr;
+      wa.e.push = push_h ? dPush : nullptr;
+      wa.e.push_joint = joint;
+      wa.lam0 = start ? hLam0 : nullptr;
+      wa.lamc_out = hLamC;
+      wa.sweeps_out = hSw;
+      wa.resid_out = hRes;
+      wa.warm_start = start ? 1 : 0;
+      wa.min_sweeps = st.min_sweeps;
+      wa.tol = st.tol;
+      ja.tau_max = dev[0];
+      ja.damping = dev[1];
+      ja.armature = dev[2];
+      ja.q_lo = dev[3];
+      ja.q_hi = dev[4];
+      ja.per_robot = per_robot;
+      ja.stops = js.stops;
+      ja.activation = js.activation;
+      ja.stop_erp = js.stop_erp;
+      ja.tau_out = hTauA;
+      ja.rows_out = hRows;
+      ja.lams_out = hLamS;
+      ja.dropped_out = hDrop;
+      run(n, ja);
+      if (v_out)
+        d2h(v_out, hV, (size_t)n * sz.nv * sizeof(double), stream);
+      if (a_out)
+        d2h(a_out, hA, (size_t)n * sz.nv * sizeof(double), stream);
+      if (lam_out)
+        d2h(lam_out, hLam, (size_t)n * gz.nrows * sizeof(double), stream);
+      if (lamc_out)
+        d2h(lamc_out, hLamC, (size_t)n * gz.nrows * sizeof(double), stream);
+      if (gap_out)
+        d2h(gap_out, hGap, (size_t)n * gz.npts * sizeof(double), stream);
+      if (con_out)
+        d2h(con_out, hCon, (size_t)n * sizeof(unsigned), stream);
+      if (sweeps_out)
+        d2h(sweeps_out, hSw, (size_t)n * sizeof(int), stream);
+      if (resid_out)
+        d2h(resid_out, hRes, (size_t)n * sizeof(double), stream);
+      if (tau_applied_out)
+        d2h(tau_applied_out, hTauA, (size_t)n * na * sizeof(double), stream);
+      if (rows_out)
+        d2h(rows_out, hRows, (size_t)n * NJ * sizeof(int), stream);
+      if (lams_out)
+        d2h(lams_out, hLamS, (size_t)n * NJ * sizeof(double), stream);
+      if (dropped_out)
+        d2h(dropped_out, hDrop, (size_t)n * sizeof(int), stream);
+      stream_sync(stream);
+    }
+  };
+} // namespace smpc

@@ -1817,6 +1817,87 @@ class BatchedRobotSim:
                                                                          con.ctypes.data, sw.ctypes.data, res.ctypes.data))
         return dict(v_next=v, a=a, lam=lam, gap=gap, contact=con, lam_contact=lamc, sweeps=sw, residual=res)
 
+    # ---- effort limits, joint damping, armature and joint-limit stops (simple-mpc_amd/csrc/smpc_sim_ground_joint_rt.h) ----
+    def _joint_model(self, n, tau_max, damping, armature, q_lo, q_hi, stops, activation, stop_erp):
+        """(smpc_joint_model_settings, the arrays it points to): arrays (na,) are broadcast, arrays (n, na) are per robot."""
+        na = self.nv - 6
+        arrs = []
+        for name, v in (("tau_max", tau_max), ("damping", damping), ("armature", armature), ("q_lo", q_lo), ("q_hi", q_hi)):
+            if v is not None:
+                v = np.ascontiguousarray(np.array(v, dtype=np.float64))
+                if v.shape != (na,) and v.shape != (n, na):
+                    raise RuntimeError("%s [na] or [%d, na] expected (na = %d)" % (name, n, na))
+            arrs.append(v)
+        per_robot = any(v is not None and v.ndim == 2 for v in arrs)
+        if per_robot:  # (one stride per call: broadcast rows beside per-robot rows are repeated)
+            arrs = [None if v is None else np.ascontiguousarray(np.broadcast_to(v, (n, na))) for v in arrs]
+        m = _capi.JointModelSettingsC()
+        for name, v in zip(("tau_max", "damping", "armature", "q_lo", "q_hi"), arrs):
+            setattr(m, name, None if v is None else v.ctypes.data)
+        m.per_robot, m.stops, m.activation, m.stop_erp = int(per_robot), int(stops), float(activation), float(stop_erp)
+        return m, arrs
+
+    def setJointModel(self, tau_max=None, damping=None, armature=None, q_lo=None, q_hi=None, stops=True, activation=0.0, stop_erp=0.0):
+        """Give the joints of every robot on the ground effort limits (tau_max >= 0, the torque applied is the demanded one clipped to
+        [-tau_max, tau_max]), implicit viscous damping (N m s / rad), armature (kg m^2) and, with stops, unilateral stops at q_lo / q_hi
+        that share the contact solve with the feet.  Arrays of shape (na,) are broadcast, arrays of shape (B, na) are per robot; None
+        stands for tau_max = inf, damping = armature = 0 and the limits of the robot table.  activation (rad; 0 stands for 0.1) is the
+        distance to a limit below which a joint gets a stop row (at most 8 per robot and step); stop_erp (0 stands for 0.2) the part of a
+        penetration removed per step.  Needs setGround first; setGround called afterwards drops the model.  From this call on
+        stepGroundDevice reports lastAppliedTorques() and lastJointStops()."""
+        m, keep = self._joint_model(self.B, tau_max, damping, armature, q_lo, q_hi, stops, activation, stop_erp)
+        self._lib.check(self._lib.L.smpc_robot_sim_set_joint_model(self._h, C.byref(m)))
+
+    def lastAppliedTorques(self):
+        """The torques applied in the last ground step [B, na] after the effort limit (host copy; joins the handle's stream); zeros
+        before setJointModel."""
+        t = np.zeros((self.B, self.nv - 6))
+        self._lib.check(self._lib.L.smpc_robot_sim_read_joint_last(self._h, t.ctypes.data, None, None, None))
+        return t
+
+    def lastJointStops(self):
+        """dict(stop_rows [B, 8] int32 (+(k + 1): joint k at its lower stop, -(k + 1): at its upper stop, 0: unused), lam_stop [B, 8]
+        (stop torques, >= 0 along the row), dropped [B] int32 (candidates beyond the 8 rows)) of the last ground step (host copy)."""
+        rows, lam, dr = np.zeros((self.B, 8), np.int32), np.zeros((self.B, 8)), np.zeros(self.B, np.int32)
+        self._lib.check(self._lib.L.smpc_robot_sim_read_joint_last(self._h, None, rows.ctypes.data, lam.ctypes.data, dr.ctypes.data))
+        return dict(stop_rows=rows, lam_stop=lam, dropped=dr)
+
+    def jointModelDevicePointers(self):
+        """(tau_applied [B][na], stop_rows [B][8] int32, lam_stop [B][8], dropped [B] int32) as device pointers owned by the handle;
+        zeros before setJointModel; they change when setGround is called again."""
+        t, r, l, d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._lib.check(self._lib.L.smpc_robot_sim_get_joint_last(self._h, C.byref(t), C.byref(r), C.byref(l), C.byref(d)))
+        return int(t.value or 0), int(r.value or 0), int(l.value or 0), int(d.value or 0)
+
+    def groundJointDynamics(self, X, tau, dt, planes=None, mu=None, push=None, joint=0, lam0=None, warm_start=None, tol=0.0, min_sweeps=0, tau_max=None,
+                            damping=None, armature=None, q_lo=None, q_hi=None, stops=True, activation=0.0, stop_erp=0.0):
+        """groundSolveDynamics with an explicit joint model per state (the arguments of setJointModel with its defaults, stops on among them;
+        arrays (na,) or (n, na)).  The
+        handle's model, settings and buffers are neither read nor changed.  Returns the dict of groundSolveDynamics and tau_applied
+        [n, na], stop_rows [n, 8] (int32), lam_stop [n, 8], dropped [n] (int32)."""
+        X = np.ascontiguousarray(np.array(X, dtype=np.float64))
+        tau = np.ascontiguousarray(np.array(tau, dtype=np.float64))
+        n = X.shape[0] if X.ndim == 2 else 0
+        if n < 1 or X.shape[1] != self.nq + self.nv or tau.shape != (n, self.nv - 6):
+            raise RuntimeError("X [n, nq + nv], tau [n, nv - 6] expected")
+        npts = self._ground_npts()
+        pl = self._env_array(planes, (n, 4), "planes [n, 4]")
+        m = self._env_array(mu, (n,), "mu [n]")
+        ps = self._env_array(push, (n, 6), "push [n, 6]")
+        l0 = self._env_array(lam0, (n, 3 * npts), "lam0 [n, 3 points]")
+        s = self._solver_settings(l0 is not None if warm_start is None else warm_start, tol, min_sweeps)
+        jm, keep = self._joint_model(n, tau_max, damping, armature, q_lo, q_hi, stops, activation, stop_erp)
+        p = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)
+        v, a, lam, lamc, gap = np.zeros((n, self.nv)), np.zeros((n, self.nv)), np.zeros((n, 3 * npts)), np.zeros((n, 3 * npts)), np.zeros((n, npts))
+        con, sw, res = np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros(n)
+        ta, rows, ls, dr = np.zeros((n, self.nv - 6)), np.zeros((n, 8), np.int32), np.zeros((n, 8)), np.zeros(n, np.int32)
+        self._lib.check(self._lib.L.smpc_robot_sim_ground_joint_dynamics(self._h, n, X, tau, float(dt), p(pl), p(m), p(ps), int(joint), C.byref(s), p(l0),
+                                                                         C.byref(jm), v.ctypes.data, a.ctypes.data, lam.ctypes.data, lamc.ctypes.data,
+                                                                         gap.ctypes.data, con.ctypes.data, sw.ctypes.data, res.ctypes.data, ta.ctypes.data,
+                                                                         rows.ctypes.data, ls.ctypes.data, dr.ctypes.data))
+        return dict(v_next=v, a=a, lam=lam, gap=gap, contact=con, lam_contact=lamc, sweeps=sw, residual=res, tau_applied=ta, stop_rows=rows, lam_stop=ls,
+                    dropped=dr)
+
 
 class FrictionCompensation:
     """reference include/simple-mpc/friction-compensation.hpp: torque += viscuous * v + dry * sign(v).  The reference reads

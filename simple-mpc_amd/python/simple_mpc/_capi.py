@@ -166,6 +166,20 @@ class GroundSolverSettingsC(C.Structure):  # smpc_ground_solver_settings
     ]
 
 
+class JointModelSettingsC(C.Structure):  # smpc_joint_model_settings
+    _fields_ = [
+        ("tau_max", C.c_void_p),
+        ("damping", C.c_void_p),
+        ("armature", C.c_void_p),
+        ("q_lo", C.c_void_p),
+        ("q_hi", C.c_void_p),
+        ("per_robot", C.c_int),
+        ("stops", C.c_int),
+        ("activation", C.c_double),
+        ("stop_erp", C.c_double),
+    ]
+
+
 # every symbol declared in include/smpc.h
 SYMBOLS = [
     "smpc_builtin_robot", "smpc_last_error", "smpc_device_count", "smpc_create", "smpc_create_centroidal", "smpc_create_fulldynamics", "smpc_get_contact_forces", "smpc_destroy", "smpc_get_dims",
@@ -183,6 +197,7 @@ SYMBOLS = [
     "smpc_robot_sim_set_ground_env", "smpc_robot_sim_set_ground_push", "smpc_robot_sim_get_ground_push", "smpc_robot_sim_ground_env_dynamics",
     "smpc_robot_sim_set_ground_solver", "smpc_robot_sim_reset_ground_warm_start", "smpc_robot_sim_reset_ground_warm_start_device", "smpc_robot_sim_get_ground_solver_last",
     "smpc_robot_sim_read_ground_solver_last", "smpc_robot_sim_ground_solve_dynamics",
+    "smpc_robot_sim_set_joint_model", "smpc_robot_sim_get_joint_last", "smpc_robot_sim_read_joint_last", "smpc_robot_sim_ground_joint_dynamics",
 ]
 
 
@@ -337,6 +352,11 @@ class SmpcLib:
         L.smpc_robot_sim_read_ground_solver_last.argtypes = [vp, vp, vp]
         L.smpc_robot_sim_ground_solve_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, vp, vp, vp, C.c_int, C.POINTER(GroundSolverSettingsC), vp, vp, vp, vp, vp,
                                                            vp, vp, vp, vp]
+        L.smpc_robot_sim_set_joint_model.argtypes = [vp, C.POINTER(JointModelSettingsC)]
+        L.smpc_robot_sim_get_joint_last.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.smpc_robot_sim_read_joint_last.argtypes = [vp, vp, vp, vp, vp]
+        L.smpc_robot_sim_ground_joint_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, vp, vp, vp, C.c_int, C.POINTER(GroundSolverSettingsC), vp,
+                                                           C.POINTER(JointModelSettingsC), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
 
     def check(self, code):
         if code < 0:
