@@ -324,6 +324,51 @@ namespace simple_mpc
                                     const std::vector<double> & planes = {}, const std::vector<double> & mu = {}, const std::vector<double> & push = {},
                                     int joint = 0, const std::vector<double> & lam0 = {}, bool warm_start = true, double tol = 0.0, int min_sweeps = 0)
     {
+      return groundJointBody(X, tau, dt, model, nullptr, planes, mu, push, joint, lam0, warm_start, tol, min_sweeps);
+    }
+
+    // ---- per-robot link masses, centres of mass and inertias (smpc_robot_sim_set_body_params and the entries after it) ----
+    // body [B][njoints][10], njoints = nq - 6: row j of robot i = mass | com x y z | Ixx Ixy Iyy Ixz Iyz Izz of the body of joint j (the
+    // layout of body_params() below).  From this call on robot i's ground step uses its rows wherever the robot table's mass, com and
+    // inertia were used; nothing else of the model changes, and the MPC and ID controllers keep the nominal table.  An empty vector clears
+    // them.  Needs setGround first; setGround called afterwards drops them.  Independent of setJointModel.
+    void setBodyParams(const std::vector<double> & body)
+    {
+      if (!body.empty() && body.size() != (size_t)batch_ * (size_t)(nq_ - 6) * 10)
+        throw std::runtime_error("body [B][njoints][10] expected (or empty)");
+      check(smpc_robot_sim_set_body_params(h_, body.empty() ? nullptr : body.data()));
+    }
+    // the body parameters in force [B][njoints][10] (host copy): those of setBodyParams, or the table's rows repeated B times
+    std::vector<double> bodyParams()
+    {
+      std::vector<double> b((size_t)batch_ * (size_t)(nq_ - 6) * 10);
+      check(smpc_robot_sim_read_body_params(h_, b.data()));
+      return b;
+    }
+    // the handle-owned device array [B][njoints][10] (null while none are set): a resident loop may rewrite it on the shared stream;
+    // values written there are not validated
+    double * bodyParamsDevicePointer()
+    {
+      double * p = nullptr;
+      check(smpc_robot_sim_get_body_params(h_, &p));
+      return p;
+    }
+    // groundJointDynamics with explicit body parameters per state: body [n][njoints][10] (empty: the robot table's); the handle's own
+    // parameters are neither read nor changed
+    GroundJoint groundBodyDynamics(const std::vector<double> & X, const std::vector<double> & tau, double dt, const JointModel & model,
+                                   const std::vector<double> & body, const std::vector<double> & planes = {}, const std::vector<double> & mu = {},
+                                   const std::vector<double> & push = {}, int joint = 0, const std::vector<double> & lam0 = {}, bool warm_start = true,
+                                   double tol = 0.0, int min_sweeps = 0)
+    {
+      return groundJointBody(X, tau, dt, model, &body, planes, mu, push, joint, lam0, warm_start, tol, min_sweeps);
+    }
+
+  private:
+    // `body` null: smpc_robot_sim_ground_joint_dynamics; else smpc_robot_sim_ground_body_dynamics
+    GroundJoint groundJointBody(const std::vector<double> & X, const std::vector<double> & tau, double dt, const JointModel & model,
+                                const std::vector<double> * body, const std::vector<double> & planes, const std::vector<double> & mu,
+                                const std::vector<double> & push, int joint, const std::vector<double> & lam0, bool warm_start, double tol, int min_sweeps)
+    {
       const size_t nx = (size_t)(nq_ + nv_), n = X.size() / nx, nr = 3 * (size_t)gn_, na = (size_t)(nv_ - 6);
       if (n == 0 || X.size() != n * nx || tau.size() != n * na)
         throw std::runtime_error("X [n][nq + nv], tau [n][nv - 6] expected");
@@ -331,6 +376,8 @@ namespace simple_mpc
         throw std::runtime_error("planes [n][4], mu [n], push [n][6] expected (or empty)");
       if (!lam0.empty() && lam0.size() != n * nr)
         throw std::runtime_error("lam0 [n][3 points] expected (or empty)");
+      if (body && !body->empty() && body->size() != n * (size_t)(nq_ - 6) * 10)
+        throw std::runtime_error("body [n][njoints][10] expected (or empty)");
       const smpc_ground_solver_settings s = {warm_start && !lam0.empty() ? 1 : 0, tol, min_sweeps};
       std::vector<double> keep[5];
       const smpc_joint_model_settings m = jointModel(model, n, keep);
@@ -347,15 +394,20 @@ namespace simple_mpc
       r.stops.stop_rows.resize(n * SMPC_JOINT_MAX_STOPS);
       r.stops.lam_stop.resize(n * SMPC_JOINT_MAX_STOPS);
       r.stops.dropped.resize(n);
-      check(smpc_robot_sim_ground_joint_dynamics(h_, (int)n, X.data(), tau.data(), dt, planes.empty() ? nullptr : planes.data(), mu.empty() ? nullptr : mu.data(),
-                                                 push.empty() ? nullptr : push.data(), joint, &s, lam0.empty() ? nullptr : lam0.data(), &m, r.s.g.v_next.data(),
-                                                 r.s.g.a.data(), r.s.g.lambda.data(), r.s.lambda_contact.data(), r.s.g.gap.data(), r.s.g.contact.data(),
-                                                 r.s.sweeps.data(), r.s.residual.data(), r.tau_applied.data(), r.stops.stop_rows.data(), r.stops.lam_stop.data(),
-                                                 r.stops.dropped.data()));
+      const double *pl = planes.empty() ? nullptr : planes.data(), *pm = mu.empty() ? nullptr : mu.data(), *pp = push.empty() ? nullptr : push.data(),
+                   *l0 = lam0.empty() ? nullptr : lam0.data();
+      if (body)
+        check(smpc_robot_sim_ground_body_dynamics(h_, (int)n, X.data(), tau.data(), dt, pl, pm, pp, joint, &s, l0, &m, body->empty() ? nullptr : body->data(),
+                                                  r.s.g.v_next.data(), r.s.g.a.data(), r.s.g.lambda.data(), r.s.lambda_contact.data(), r.s.g.gap.data(),
+                                                  r.s.g.contact.data(), r.s.sweeps.data(), r.s.residual.data(), r.tau_applied.data(), r.stops.stop_rows.data(),
+                                                  r.stops.lam_stop.data(), r.stops.dropped.data()));
+      else
+        check(smpc_robot_sim_ground_joint_dynamics(h_, (int)n, X.data(), tau.data(), dt, pl, pm, pp, joint, &s, l0, &m, r.s.g.v_next.data(), r.s.g.a.data(),
+                                                   r.s.g.lambda.data(), r.s.lambda_contact.data(), r.s.g.gap.data(), r.s.g.contact.data(), r.s.sweeps.data(),
+                                                   r.s.residual.data(), r.tau_applied.data(), r.stops.stop_rows.data(), r.stops.lam_stop.data(),
+                                                   r.stops.dropped.data()));
       return r;
     }
-
-  private:
     // the C struct of a JointModel for `rows` robots; with one per-robot array the broadcast ones are repeated into `keep` (one stride per call)
     smpc_joint_model_settings jointModel(const JointModel & model, size_t rows, std::vector<double> (&keep)[5]) const
     {
@@ -400,4 +452,36 @@ namespace simple_mpc
     smpc_robot_sim * h_ = nullptr;
     int batch_ = 0, nq_ = 0, nv_ = 0, nf_ = 0, fs_ = 0, gp_ = 0, gn_ = 0;
   };
+
+  // ---- host helpers for body parameters (plain C++, no GPU) ----
+  // the body parameters [njoints][10] of a robot table: mass | com x y z | Ixx Ixy Iyy Ixz Iyz Izz per joint
+  inline std::vector<double> body_params(const smpc_robot_model * robot)
+  {
+    std::vector<double> b((size_t)robot->njoints * 10);
+    for (int j = 0; j < robot->njoints; j++)
+    {
+      b[(size_t)j * 10] = robot->mass[j];
+      for (int k = 0; k < 3; k++)
+        b[(size_t)j * 10 + 1 + k] = robot->com[j][k];
+      for (int k = 0; k < 6; k++)
+        b[(size_t)j * 10 + 4 + k] = robot->inertia[j][k];
+    }
+    return b;
+  }
+  // body [rows][10] with mass and inertia of row r multiplied by mass_scale[r % mass_scale.size()] (one factor, one per joint, or one per
+  // row); the centres of mass are unchanged
+  inline std::vector<double> scale_bodies(const std::vector<double> & body, const std::vector<double> & mass_scale)
+  {
+    if (body.size() % 10 != 0 || mass_scale.empty() || (body.size() / 10) % mass_scale.size() != 0)
+      throw std::runtime_error("scale_bodies: body [rows][10] and mass_scale [1], [njoints] or [rows] expected");
+    std::vector<double> out = body;
+    for (size_t r = 0; r < body.size() / 10; r++)
+    {
+      const double s = mass_scale[r % mass_scale.size()];
+      out[r * 10] *= s;
+      for (int k = 4; k < 10; k++)
+        out[r * 10 + k] *= s;
+    }
+    return out;
+  }
 } // namespace simple_mpc

@@ -769,6 +769,39 @@ int smpc_robot_sim_ground_joint_dynamics(smpc_robot_sim * sim, int n, const doub
                                          double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out, double * residual_out,
                                          double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out);
 
+/* ---- per-robot link masses, centres of mass and inertias on that ground (simple-mpc_amd/csrc/smpc_sim_ground_joint_rt.h:
+ * sim_ground_body_rt_body) ----
+ * A handle that has a ground gets optional BODY PARAMETERS: body [B][njoints][10] doubles, njoints the robot's own joint count (nq - 6,
+ * the free-flyer included).  Row j of robot i is [mass, com_x, com_y, com_z, Ixx, Ixy, Iyy, Ixz, Iyz, Izz]: order and meaning of mass[j],
+ * com[j], inertia[j] of smpc_robot.h (com in the joint frame, inertia about the body's CoM in the joint frame).  A row is admitted exactly
+ * when a robot table carrying it would be: mass finite and > 0, com finite, inertia finite.
+ * When body parameters are set, robot i's ground step uses row [i][j] wherever the kernels use the table's mass[j], com[j], inertia[j]:
+ * the spatial inertia of body j, hence M, h and everything computed from them.  Nothing else of the model changes: tree, placements,
+ * feet, the contact model of DESIGN 3.23 - 3.25 and the joint model of 3.26 stay as written.  A step with the rows of a table equals, bit
+ * for bit, the step of a handle created from that table.  The MPC and the inverse-dynamics controllers keep the table they were created
+ * with.  The free-flight entries (smpc_robot_sim_step_device, smpc_robot_sim_forward_dynamics) do not read body parameters.
+ * Each entry validates before it allocates, answers SMPC_ERR_INVALID with a message that names the field and the first offending
+ * [robot][joint], and leaves the previous parameters in force.
+ *   smpc_robot_sim_set_body_params    stores body [B][njoints][10] (host, copied); NULL clears.  Needs smpc_robot_sim_set_ground first;
+ *                            smpc_robot_sim_set_ground called afterwards DROPS the parameters.  Independent of
+ *                            smpc_robot_sim_set_joint_model, in either order.  While they are set smpc_robot_sim_step_ground_device launches
+ *                            sim_ground_body_rt_body with the handle's joint model, or with the inert one if it has none; once cleared, the
+ *                            handle launches exactly what it launched before.  Joins the handle's stream first.
+ *   smpc_robot_sim_read_body_params   a host copy [B][njoints][10]; the table's rows repeated B times while nothing is set.
+ *   smpc_robot_sim_get_body_params    the handle-owned device pointer, NULL while unset.  A resident loop may rewrite the array on the shared
+ *                            stream; values written there are NOT validated (a non-finite value gives NaNs in that robot's outputs).
+ *   smpc_robot_sim_ground_body_dynamics   smpc_robot_sim_ground_joint_dynamics plus body [n][njoints][10] (NULL: the table's).  The handle's
+ *                            own parameters are neither read nor changed, and n need not be the batch. */
+int smpc_robot_sim_set_body_params(smpc_robot_sim * sim, const double * body);
+int smpc_robot_sim_read_body_params(smpc_robot_sim * sim, double * body_out);
+int smpc_robot_sim_get_body_params(smpc_robot_sim * sim, double ** body_device);
+int smpc_robot_sim_ground_body_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const double * plane, const double * mu,
+                                        const double * push, int push_joint, const smpc_ground_solver_settings * settings, const double * lambda0,
+                                        const smpc_joint_model_settings * model, const double * body, double * v_next_out, double * a_out,
+                                        double * lambda_out, double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out,
+                                        double * residual_out, double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out,
+                                        int32_t * dropped_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,9 @@ struct smpc_robot_sim // stand-alone simulator handle: a robot table and nothing
   std::unique_ptr<RobotSimGroundEnv> ge; // its per-robot environment and the staging of the host-buffer solve (destroyed before the ground it refers to)
   std::unique_ptr<RobotSimGroundWs> gw;  // its solver settings, warm buffer and read-outs (destroyed before the ground it refers to)
   std::unique_ptr<RobotSimGroundJoint> gj; // its joint model and read-outs (destroyed before the ground it refers to)
+  std::unique_ptr<RobotSimGroundBody> gb;  // its per-robot body parameters (destroyed before the ground it refers to)
   std::vector<double> q_lo, q_hi;        // the robot table's joint limits [nv - 6]: the joint model's defaults
+  std::vector<double> body_tab;          // the robot table's mass | com | inertia rows [njoints][10]: what is read while no body parameters are set
 };
 
 struct smpc_handle
@@ -186,6 +188,12 @@ namespace
              "those of the iterate before the reset; run iterate first";
     return nullptr;
   }
+  // the host-buffer solve behind smpc_robot_sim_ground_joint_dynamics (body null) and smpc_robot_sim_ground_body_dynamics
+  int ground_joint_body_dynamics(const char * who, smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const double * plane,
+                                 const double * mu, const double * push, int push_joint, const smpc_ground_solver_settings * settings, const double * lambda0,
+                                 const smpc_joint_model_settings * model, const double * body, double * v_next_out, double * a_out, double * lambda_out,
+                                 double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out, double * residual_out,
+                                 double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out);
 } // namespace
 
 extern "C"
@@ -1225,6 +1233,8 @@ extern "C"
       h->e.reset(new RobotSimRt(robot, force_size, batch, gravity, device_id));
       h->q_lo.assign(robot->q_lo, robot->q_lo + h->e->sz.na);
       h->q_hi.assign(robot->q_hi, robot->q_hi + h->e->sz.na);
+      h->body_tab.resize((size_t)robot->njoints * SIM_BODY_ROW);
+      sim_body_table_rows(robot, h->body_tab.data());
       *out = h.release();
     });
   }
@@ -1308,6 +1318,7 @@ extern "C"
       sim->ge.reset(); // (the per-robot environment and the push go with the ground they were set on)
       sim->gw.reset(); // (and so do the solver settings and the warm buffer)
       sim->gj.reset(); // (and the joint model)
+      sim->gb.reset(); // (and the body parameters)
       sim->g = std::move(g);
     });
   }
@@ -1327,6 +1338,12 @@ extern "C"
       return fail(SMPC_ERR_INVALID, "smpc_robot_sim_step_ground_device: no ground yet, call smpc_robot_sim_set_ground first");
     if (!(dt > 0.0) || !std::isfinite(dt))
       return fail(SMPC_ERR_INVALID, "dt must be positive");
+    if (sim->gb && sim->gb->active) // (body parameters have been set: sim_ground_body_rt_body with the joint model if there is one, else the inert one)
+      return guarded([&] {
+        if (!sim->gj)
+          sim->gj.reset(new RobotSimGroundJoint(*sim->g)); // (its arrays stay null: nothing is allocated)
+        sim->gj->step_device(X_device, tau_device, dt, sim->ge.get(), sim->gw.get(), sim->gb->body);
+      });
     if (sim->gj && sim->gj->active) // (a joint model has been set: sim_ground_joint_rt_body, which reads the environment and the solver settings if there are any)
       return guarded([&] { sim->gj->step_device(X_device, tau_device, dt, sim->ge.get(), sim->gw.get()); });
     if (sim->gw && sim->gw->active) // (solver settings have been set: sim_ground_ws_rt_body, which reads the environment if there is one)
@@ -1608,10 +1625,73 @@ extern "C"
                                            double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out, double * residual_out,
                                            double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out)
   {
+    return ground_joint_body_dynamics("smpc_robot_sim_ground_joint_dynamics", sim, n, X, tau, dt, plane, mu, push, push_joint, settings, lambda0, model, nullptr,
+                                      v_next_out, a_out, lambda_out, lambda_contact_out, gap_out, contact_out, sweeps_out, residual_out, tau_applied_out,
+                                      stop_rows_out, lam_stop_out, dropped_out);
+  }
+
+  // ---- per-robot link masses, centres of mass and inertias (smpc_sim_ground_joint_rt.h: sim_ground_body_rt_body) ----
+  int smpc_robot_sim_set_body_params(smpc_robot_sim * sim, const double * body)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_set_body_params: no ground yet, call smpc_robot_sim_set_ground first");
+    // admission before anything else: nothing is allocated, and the previous parameters stay, for rows a robot table could not carry
+    const std::string why = sim_body_admission_error(sim->e->B, sim->e->sz.nq - 6, body);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      if (!sim->gb)
+      {
+        if (!body) // (nothing to clear, nothing allocated)
+          return;
+        sim->gb.reset(new RobotSimGroundBody(*sim->g));
+      }
+      sim->gb->set(body);
+    });
+  }
+  int smpc_robot_sim_read_body_params(smpc_robot_sim * sim, double * body_out)
+  {
+    if (!sim || !body_out)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (sim->gb && sim->gb->active)
+      return guarded([&] { sim->gb->read(body_out); });
+    for (int i = 0; i < sim->e->B; i++) // (the table's rows, without allocating or joining the stream)
+      std::memcpy(body_out + (size_t)i * sim->body_tab.size(), sim->body_tab.data(), sim->body_tab.size() * sizeof(double));
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_get_body_params(smpc_robot_sim * sim, double ** body_device)
+  {
+    if (!sim || !body_device)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    *body_device = sim->gb && sim->gb->active ? sim->gb->body : nullptr;
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_ground_body_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const double * plane, const double * mu,
+                                          const double * push, int push_joint, const smpc_ground_solver_settings * settings, const double * lambda0,
+                                          const smpc_joint_model_settings * model, const double * body, double * v_next_out, double * a_out, double * lambda_out,
+                                          double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out, double * residual_out,
+                                          double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out)
+  {
+    return ground_joint_body_dynamics("smpc_robot_sim_ground_body_dynamics", sim, n, X, tau, dt, plane, mu, push, push_joint, settings, lambda0, model, body,
+                                      v_next_out, a_out, lambda_out, lambda_contact_out, gap_out, contact_out, sweeps_out, residual_out, tau_applied_out,
+                                      stop_rows_out, lam_stop_out, dropped_out);
+  }
+}
+
+namespace
+{
+  int ground_joint_body_dynamics(const char * who, smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const double * plane,
+                                 const double * mu, const double * push, int push_joint, const smpc_ground_solver_settings * settings, const double * lambda0,
+                                 const smpc_joint_model_settings * model, const double * body, double * v_next_out, double * a_out, double * lambda_out,
+                                 double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out, double * residual_out,
+                                 double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out)
+  {
     if (!sim || !X || !tau)
       return fail(SMPC_ERR_INVALID, "null argument");
     if (!sim->g)
-      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_ground_joint_dynamics: no ground yet, call smpc_robot_sim_set_ground first");
+      return fail(SMPC_ERR_INVALID, std::string(who) + ": no ground yet, call smpc_robot_sim_set_ground first");
     if (n < 1)
       return fail(SMPC_ERR_INVALID, "n must be positive");
     if (!(dt > 0.0) || !std::isfinite(dt))
@@ -1625,14 +1705,23 @@ extern "C"
       why = sim_ground_push_admission_error(n, sim->e->sz.nq - 6, push_joint, push);
     if (why.empty())
       why = sim_joint_admission_error(n, sim->e->sz.na, sim->q_lo.data(), sim->q_hi.data(), model);
+    if (why.empty())
+      why = sim_body_admission_error(n, sim->e->sz.nq - 6, body);
     if (!why.empty())
       return fail(SMPC_ERR_INVALID, why);
     return guarded([&] {
       if (!sim->gj)
         sim->gj.reset(new RobotSimGroundJoint(*sim->g)); // (staging only: the handle's ground steps keep their kernel until the setter is called)
+      const double * body_dev = nullptr;
+      if (body)
+      {
+        if (!sim->gb)
+          sim->gb.reset(new RobotSimGroundBody(*sim->g)); // (staging only, likewise)
+        body_dev = sim->gb->stage(n, body);
+      }
       sim->gj->dynamics(n, X, tau, dt, plane, mu, push, push_joint, sim_ground_ws_resolve(st), lambda0, model, sim->q_lo.data(), sim->q_hi.data(),
                         v_next_out, a_out, lambda_out, lambda_contact_out, gap_out, contact_out, sweeps_out, residual_out, tau_applied_out, stop_rows_out,
-                        lam_stop_out, dropped_out);
+                        lam_stop_out, dropped_out, body_dev);
     });
   }
-}
+} // namespace

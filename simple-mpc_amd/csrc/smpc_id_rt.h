@@ -67,7 +67,11 @@ namespace smpc
   // joint (one step per tree level), body inertias and forces f = I (a - g) + v x* (I v) under the gravity field g, foot positions, the
   // sums over the subtree of every joint through the ancestor bit sets, F_d = Ic S_d and h_d = S_d . f (the bias forces).  Its first phase
   // issues every global load it makes; it stores nothing outside `sc`.
-  SMPC_DEV void rt_tree_phases(IdQuantRtScratch & sc, const IdRtDevModel & mi, const double * x, const V3 g)
+  // BODY: lane j takes mass, com and inertia of its body from `rows` + 10 j (device, [nj][10] doubles of ONE robot in the
+  // order mass | com | Ixx Ixy Iyy Ixz Iyz Izz: 80 contiguous bytes per lane) instead of from the device table; a null `rows` (wave-uniform)
+  // reads the table.  The values enter arithmetic only, never an index.  BODY = false is the walk every other kernel uses.
+  template <bool BODY>
+  SMPC_DEV void rt_tree_phases_impl(IdQuantRtScratch & sc, const IdRtDevModel & mi, const double * x, const V3 g, const double * rows)
   {
     typedef IdQuantRtScratch SC;
     constexpr int NT = 64, MAXJ = SC::MAXJ, MAXV = SC::MAXV, NF = SC::NF;
@@ -88,16 +92,28 @@ namespace smpc
 #pragma unroll
       for (int i = 0; i < 9; i++)
         SMPC_PLV(jg)[i] = mg.jpR[j][i];
-#pragma unroll
-      for (int i = 0; i < 3; i++)
+      if (BODY && rows != nullptr)
       {
-        SMPC_PLV(jg)[9 + i] = mg.jpp[j][i];
-        SMPC_PLV(jg)[13 + i] = mg.com[j][i];
-      }
-      SMPC_PLV(jg)[12] = mg.mass[j];
 #pragma unroll
-      for (int i = 0; i < 6; i++)
-        SMPC_PLV(jg)[16 + i] = mg.inertia[j][i];
+        for (int i = 0; i < 3; i++)
+          SMPC_PLV(jg)[9 + i] = mg.jpp[j][i];
+#pragma unroll
+        for (int i = 0; i < 10; i++)
+          SMPC_PLV(jg)[12 + i] = rows[(size_t)j * 10 + i];
+      }
+      else
+      {
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+        {
+          SMPC_PLV(jg)[9 + i] = mg.jpp[j][i];
+          SMPC_PLV(jg)[13 + i] = mg.com[j][i];
+        }
+        SMPC_PLV(jg)[12] = mg.mass[j];
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+          SMPC_PLV(jg)[16 + i] = mg.inertia[j][i];
+      }
       const int p = mg.parent[j];
       SMPC_PLV(par) = p >= 0 && p < nj ? p : 0;
       SMPC_PLV(jt) = mg.jtype[j];
@@ -232,6 +248,10 @@ namespace smpc
       sc.h[d] = id_rt_dot6(&sc.S[d * 6], &sc.fs[jd * 6]);
     }
     SMPC_LANES_END_WAVE
+  }
+  SMPC_DEV void rt_tree_phases(IdQuantRtScratch & sc, const IdRtDevModel & mi, const double * x, const V3 g)
+  {
+    rt_tree_phases_impl<false>(sc, mi, x, g, nullptr);
   }
 
   // ---- kernel 1: rigid-body quantities on the run-time tree ----   grid = B, 64 lanes

@@ -14,9 +14,14 @@
 // NROWS counts contact rows AND stop rows: <24> serves up to 12 contact rows (5 points fit), <32> up to 24, each with 8 stop rows.
 // With tau_max = +inf, d = r_a = 0 and stops = 0 every added term is an exact zero and the results equal the sibling's bit for bit.
 // LDS: IdQuantRtScratch (19 024 B) + SimGroundJointLds<NROWS> = SimGroundWsLds<NROWS> + 4 (nv_max - 6) + 8 doubles + 18 ints.
+// PER-ROBOT BODY PARAMETERS: sim_ground_body_rt_body<NROWS> is the same source compiled with BODY = true.  Its tree walk
+// loads mass, com and inertia of body j of robot i from body[i][j][0..9] (global memory -> registers of lane j, in the walk's first phase)
+// instead of from the device table; every other instruction is shared, the LDS is the same, and sim_ground_joint_rt_body compiles to
+// what it compiled to before the flag existed.
 #pragma once
 #include "smpc_sim_ground_ws_rt.h"
 #include "smpc_sim_joint_dims.h"
+#include "smpc_sim_body_dims.h"
 #include <vector>
 
 namespace smpc
@@ -50,9 +55,11 @@ namespace smpc
   static_assert(sizeof(IdQuantRtScratch) + sizeof(SimGroundJointLds<24>) <= 163840 / 3, "three blocks per compute unit");
   static_assert(sizeof(IdQuantRtScratch) + sizeof(SimGroundJointLds<32>) <= 163840 / 2, "two blocks per compute unit");
 
-  // grid = n, 64 lanes
-  template <int NROWS>
-  SMPC_DEV void sim_ground_joint_rt_body(const SimGroundJointArgs & ja, int block)
+  // The one body of the step.  BODY = false is sim_ground_joint_rt_body; BODY = true is sim_ground_body_rt_body: `body` is
+  // [n][nj][10] doubles on the device, and the tree walk of robot `inst` takes mass, com and inertia of body j from row [inst][j] instead
+  // of from the device table (a null `body` reads the table; nj is the clamped joint count of the device table).  Nothing else differs.
+  template <int NROWS, bool BODY>
+  SMPC_DEV void sim_ground_joint_rt_impl(const SimGroundJointArgs & ja, const double * body, int block)
   {
     typedef IdQuantRtScratch SC;
     typedef SimGroundLds<NROWS> L;
@@ -132,7 +139,11 @@ namespace smpc
     }
     SMPC_LANES_END_WAVE
     // ---- phases 1, 2 ----
-    rt_tree_phases(sc, mi, ka.X + (size_t)inst * nx, mk3(ka.gravity[0], ka.gravity[1], ka.gravity[2]));
+    if constexpr (BODY) // (the pointer is null-checked once, wave-uniformly: it is a kernel argument)
+      rt_tree_phases_impl<true>(sc, mi, ka.X + (size_t)inst * nx, mk3(ka.gravity[0], ka.gravity[1], ka.gravity[2]),
+                                body != nullptr ? body + (size_t)inst * nj * 10 : nullptr);
+    else
+      rt_tree_phases(sc, mi, ka.X + (size_t)inst * nx, mk3(ka.gravity[0], ka.gravity[1], ka.gravity[2]));
     // ---- Mh = M + diag(0_6, r_a + dt d) (both triangles from one expression: symmetric bit for bit); contact points, gaps, frame and push
     // point; the stop candidates ----
     SMPC_LANES(NT)
@@ -527,6 +538,27 @@ namespace smpc
     SMPC_LANES_END_WAVE
   }
 
+  // grid = n, 64 lanes
+  template <int NROWS>
+  SMPC_DEV void sim_ground_joint_rt_body(const SimGroundJointArgs & ja, int block)
+  {
+    sim_ground_joint_rt_impl<NROWS, false>(ja, nullptr, block);
+  }
+
+  // ---- per-robot body parameters: the same step with the masses, centres of mass and inertias of robot i from body[i] ----
+  struct SimGroundBodyArgs
+  {
+    SimGroundJointArgs j;
+    const double * body; // [n][nj][10] (device): mass | com | Ixx Ixy Iyy Ixz Iyz Izz of every body, or null: the device table
+  };
+  // (no LDS of its own: the rows go from global memory to the registers of lane j, so the bounds asserted above hold unchanged)
+  // grid = n, 64 lanes
+  template <int NROWS>
+  SMPC_DEV void sim_ground_body_rt_body(const SimGroundBodyArgs & ba, int block)
+  {
+    sim_ground_joint_rt_impl<NROWS, true>(ba.j, ba.body, block);
+  }
+
   // ---- host: the joint model and the per-robot read-outs of one simulator handle's ground (a sibling of RobotSimGroundWs; the
   // environment and the solver state of a step are handed in by the caller).  `active` once the setter has been called: from then on the
   // handle's ground steps launch the kernel above.  The host-buffer solve needs no setter, allocates its staging only and never touches the
@@ -647,15 +679,27 @@ namespace smpc
       sc = sim_joint_resolve(m);
       active = true;
     }
-    void run(int n, const SimGroundJointArgs & ja)
+    // `body` ([n][njoints][10] on the device) non-null: sim_ground_body_rt_body, else the kernel of DESIGN 3.26
+    void run(int n, const SimGroundJointArgs & ja, const double * body = nullptr)
     {
-      if (g.gz.inst == 12)
+      if (body != nullptr)
+      {
+        SimGroundBodyArgs ba;
+        ba.j = ja;
+        ba.body = body;
+        if (g.gz.inst == 12)
+          launch<SimGroundBodyArgs, sim_ground_body_rt_body<24>, 64, 1, 0>(n, g.sim.stream, ba);
+        else
+          launch<SimGroundBodyArgs, sim_ground_body_rt_body<32>, 64, 1, 0>(n, g.sim.stream, ba);
+      }
+      else if (g.gz.inst == 12)
         launch<SimGroundJointArgs, sim_ground_joint_rt_body<24>, 64, 1, 0>(n, g.sim.stream, ja);
       else
         launch<SimGroundJointArgs, sim_ground_joint_rt_body<32>, 64, 1, 0>(n, g.sim.stream, ja);
     }
-    // `env` and `ws` may be null or inactive: the handle's uniform ground, no push; `sweeps` sweeps from zero
-    void step_device(double * X_dev, const double * tau_dev, double dt, const RobotSimGroundEnv * env, RobotSimGroundWs * ws)
+    // `env` and `ws` may be null or inactive: the handle's uniform ground, no push; `sweeps` sweeps from zero.  Before set_model every
+    // array is null and stops = 0: the inert model (a handle with body parameters and no joint model steps through here).
+    void step_device(double * X_dev, const double * tau_dev, double dt, const RobotSimGroundEnv * env, RobotSimGroundWs * ws, const double * body = nullptr)
     {
       RobotSimRt & sim = g.sim;
       set_device(sim.device_id);
@@ -694,7 +738,7 @@ namespace smpc
       ja.rows_out = rows;
       ja.lams_out = lams;
       ja.dropped_out = dropped;
-      run(sim.B, ja);
+      run(sim.B, ja, body);
     }
     void read_last(double * tau_out, int * rows_out, double * lams_out, int * dropped_out)
     {
@@ -719,11 +763,11 @@ namespace smpc
       staging.back() = p;
       return p;
     }
-    // (the caller has run the admissions) `m` may be null: the inert model
+    // (the caller has run the admissions) `m` may be null: the inert model; `body_dev` ([n][njoints][10], device, complete on the stream) or null
     void dynamics(int n, const double * X, const double * tau, double dt, const double * plane_h, const double * mu_h, const double * push_h, int joint,
                   const SimGroundWsSettings & st, const double * lam0_h, const smpc_joint_model_settings * m, const double * tab_lo, const double * tab_hi,
                   double * v_out, double * a_out, double * lam_out, double * lamc_out, double * gap_out, unsigned * con_out, int * sweeps_out, double * resid_out,
-                  double * tau_applied_out, int * rows_out, double * lams_out, int * dropped_out)
+                  double * tau_applied_out, int * rows_out, double * lams_out, int * dropped_out, const double * body_dev = nullptr)
     {
       if (n < 1)
         throw InvalidCall("n must be positive");
@@ -839,7 +883,7 @@ namespace smpc
       ja.rows_out = hRows;
       ja.lams_out = hLamS;
       ja.dropped_out = hDrop;
-      run(n, ja);
+      run(n, ja, body_dev);
       if (v_out)
         d2h(v_out, hV, (size_t)n * sz.nv * sizeof(double), stream);
       if (a_out)
@@ -865,6 +909,70 @@ namespace smpc
       if (dropped_out)
         d2h(dropped_out, hDrop, (size_t)n * sizeof(int), stream);
       stream_sync(stream);
+    }
+  };
+
+  // ---- host: the per-robot body parameters of one simulator handle's ground (a sibling of RobotSimGroundJoint, whose
+  // step_device and dynamics take the device pointers handed out here).  `active` between set(rows) and set(null): while it is, the
+  // handle's ground steps launch sim_ground_body_rt_body.  The staging of the host-buffer solve never touches the handle's own array. ----
+  struct RobotSimGroundBody
+  {
+    RobotSimGround & g;
+    bool active = false;
+    double * body = nullptr;  // [B][njoints][10], kept once allocated (the pointer handed out stays valid across set calls)
+    double * hBody = nullptr; // host-buffer form: [cap][njoints][10], grown on demand
+    int cap = 0;
+
+    explicit RobotSimGroundBody(RobotSimGround & ground) : g(ground) {}
+    RobotSimGroundBody(const RobotSimGroundBody &) = delete;
+    RobotSimGroundBody & operator=(const RobotSimGroundBody &) = delete;
+    ~RobotSimGroundBody()
+    {
+      dev_free(body);
+      dev_free(hBody);
+    }
+    int njoints() const { return g.sim.sz.nq - 6; }
+    // (the caller has run sim_body_admission_error) rows [B][njoints][10] to the device; null clears: the handle launches what it launched before
+    void set(const double * rows)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      sim.wait(); // (a step in flight still reads the array)
+      if (!rows)
+      {
+        active = false;
+        return;
+      }
+      const size_t bytes = sim_body_bytes(sim.B, njoints());
+      if (!body)
+        body = (double *)dev_alloc(bytes);
+      h2d(body, rows, bytes, sim.stream);
+      stream_sync(sim.stream);
+      active = true;
+    }
+    void read(double * out)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      d2h(out, body, sim_body_bytes(sim.B, njoints()), sim.stream);
+      stream_sync(sim.stream);
+    }
+    // rows [n][njoints][10] of a host-buffer solve to the staging array, on the handle's stream; the device pointer for RobotSimGroundJoint::dynamics
+    const double * stage(int n, const double * rows)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      if (n > cap)
+      {
+        stream_sync(sim.stream);
+        dev_free(hBody);
+        hBody = nullptr;
+        cap = 0;
+        hBody = (double *)dev_alloc(sim_body_bytes(n, njoints()));
+        cap = n;
+      }
+      h2d(hBody, rows, sim_body_bytes(n, njoints()), sim.stream);
+      return hBody;
     }
   };
 } // namespace smpc

@@ -198,6 +198,7 @@ SYMBOLS = [
     "smpc_robot_sim_set_ground_solver", "smpc_robot_sim_reset_ground_warm_start", "smpc_robot_sim_reset_ground_warm_start_device", "smpc_robot_sim_get_ground_solver_last",
     "smpc_robot_sim_read_ground_solver_last", "smpc_robot_sim_ground_solve_dynamics",
     "smpc_robot_sim_set_joint_model", "smpc_robot_sim_get_joint_last", "smpc_robot_sim_read_joint_last", "smpc_robot_sim_ground_joint_dynamics",
+    "smpc_robot_sim_set_body_params", "smpc_robot_sim_read_body_params", "smpc_robot_sim_get_body_params", "smpc_robot_sim_ground_body_dynamics",
 ]
 
 
@@ -357,6 +358,11 @@ class SmpcLib:
         L.smpc_robot_sim_read_joint_last.argtypes = [vp, vp, vp, vp, vp]
         L.smpc_robot_sim_ground_joint_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, vp, vp, vp, C.c_int, C.POINTER(GroundSolverSettingsC), vp,
                                                            C.POINTER(JointModelSettingsC), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.smpc_robot_sim_set_body_params.argtypes = [vp, vp]
+        L.smpc_robot_sim_read_body_params.argtypes = [vp, _dp]
+        L.smpc_robot_sim_get_body_params.argtypes = [vp, C.POINTER(vp)]
+        L.smpc_robot_sim_ground_body_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, vp, vp, vp, C.c_int, C.POINTER(GroundSolverSettingsC), vp,
+                                                          C.POINTER(JointModelSettingsC), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
 
     def check(self, code):
         if code < 0:
