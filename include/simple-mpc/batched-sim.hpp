@@ -5,6 +5,7 @@
 #pragma once
 #include "../smpc.h"
 #include "batched-mpc.hpp"
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -363,11 +364,100 @@ namespace simple_mpc
       return groundJointBody(X, tau, dt, model, &body, planes, mu, push, joint, lam0, warm_start, tol, min_sweeps);
     }
 
+    // ---- per-robot height-field terrain (smpc_robot_sim_set_terrain and the entries after it) ----
+    // heights [tiles][ny][nx] are world z at the grid nodes (row j along world y, column i along world x, `cell` metres apart); tile [B]
+    // says which tile robot i stands on (empty: 0) and origin [B][2] is the world (x, y) of node (0, 0) of its tile (empty: (0, 0)).
+    struct Terrain
+    {
+      int nx = 0, ny = 0, tiles = 1;
+      double cell = 0.0;
+      std::vector<double> heights;
+      std::vector<int32_t> tile;
+      std::vector<double> origin;
+    };
+    // From this call on every contact point has its own normal, contact frame and gap, sampled from the bilinear patch below it
+    // (terrain_height() below is the same sampling); mu, the push, the solver settings, the joint model and the body parameters are
+    // unchanged, and the planes of setGroundEnv are not read.  Needs setGround first; setGround called afterwards drops the terrain.
+    void setTerrain(const Terrain & t)
+    {
+      const smpc_terrain_settings c = terrainSettings(t, (size_t)batch_);
+      check(smpc_robot_sim_set_terrain(h_, &c));
+    }
+    // the handle launches what it launched before setTerrain
+    void clearTerrain() { check(smpc_robot_sim_set_terrain(h_, nullptr)); }
+    // the handle-owned device arrays and the dims (null / 0 while no terrain is set): a resident loop may rewrite the arrays on the shared
+    // stream; values written there are not validated, and the kernel's clamps keep every index inside the array
+    struct TerrainDevice
+    {
+      double * heights = nullptr;
+      int32_t * tile = nullptr;
+      double * origin = nullptr;
+      int32_t nx = 0, ny = 0, tiles = 0;
+      double cell = 0.0;
+    };
+    TerrainDevice terrainDevicePointers()
+    {
+      TerrainDevice d;
+      check(smpc_robot_sim_get_terrain(h_, &d.heights, &d.tile, &d.origin, &d.nx, &d.ny, &d.tiles, &d.cell));
+      return d;
+    }
+    // the unit normal of the terrain below every contact point at the last ground step [B][points][3] (host copy)
+    std::vector<double> lastTerrainNormals()
+    {
+      std::vector<double> n((size_t)batch_ * (size_t)gn_ * 3);
+      check(smpc_robot_sim_read_terrain_last(h_, n.data(), nullptr));
+      return n;
+    }
+    // the terrain height below every contact point at the last ground step [B][points] (host copy)
+    std::vector<double> lastTerrainHeights()
+    {
+      std::vector<double> h((size_t)batch_ * (size_t)gn_);
+      check(smpc_robot_sim_read_terrain_last(h_, nullptr, h.data()));
+      return h;
+    }
+    struct GroundTerrain
+    {
+      GroundJoint j;
+      std::vector<double> normals, heights; // [n][points][3], [n][points]
+    };
+    // groundBodyDynamics on a terrain instead of planes (tile [n], origin [n][2]); the handle's own terrain is neither read nor changed
+    GroundTerrain groundTerrainDynamics(const std::vector<double> & X, const std::vector<double> & tau, double dt, const Terrain & terrain,
+                                        const JointModel & model, const std::vector<double> & body = {}, const std::vector<double> & mu = {},
+                                        const std::vector<double> & push = {}, int joint = 0, const std::vector<double> & lam0 = {}, bool warm_start = true,
+                                        double tol = 0.0, int min_sweeps = 0)
+    {
+      const size_t n = X.size() / (size_t)(nq_ + nv_);
+      const smpc_terrain_settings c = terrainSettings(terrain, n);
+      GroundTerrain r;
+      r.normals.resize(n * (size_t)gn_ * 3);
+      r.heights.resize(n * (size_t)gn_);
+      r.j = groundJointBody(X, tau, dt, model, &body, {}, mu, push, joint, lam0, warm_start, tol, min_sweeps, &c, r.normals.data(), r.heights.data());
+      return r;
+    }
+
   private:
-    // `body` null: smpc_robot_sim_ground_joint_dynamics; else smpc_robot_sim_ground_body_dynamics
+    smpc_terrain_settings terrainSettings(const Terrain & t, size_t rows) const
+    {
+      if (t.nx < 0 || t.ny < 0 || t.tiles < 0 || t.heights.size() != (size_t)t.tiles * (size_t)t.ny * (size_t)t.nx)
+        throw std::runtime_error("heights [tiles][ny][nx] expected");
+      if ((!t.tile.empty() && t.tile.size() != rows) || (!t.origin.empty() && t.origin.size() != rows * 2))
+        throw std::runtime_error("tile [rows], origin [rows][2] expected (or empty)");
+      smpc_terrain_settings c;
+      c.nx = t.nx;
+      c.ny = t.ny;
+      c.tiles = t.tiles;
+      c.cell = t.cell;
+      c.heights = t.heights.empty() ? nullptr : t.heights.data();
+      c.tile = t.tile.empty() ? nullptr : t.tile.data();
+      c.origin = t.origin.empty() ? nullptr : t.origin.data();
+      return c;
+    }
+    // `terrain` non-null: smpc_robot_sim_ground_terrain_dynamics; else `body` null: smpc_robot_sim_ground_joint_dynamics; else
+    // smpc_robot_sim_ground_body_dynamics
     GroundJoint groundJointBody(const std::vector<double> & X, const std::vector<double> & tau, double dt, const JointModel & model,
                                 const std::vector<double> * body, const std::vector<double> & planes, const std::vector<double> & mu,
-                                const std::vector<double> & push, int joint, const std::vector<double> & lam0, bool warm_start, double tol, int min_sweeps)
+                                const std::vector<double> & push, int joint, const std::vector<double> & lam0, bool warm_start, double tol, int min_sweeps,
+                                const smpc_terrain_settings * terrain = nullptr, double * normals_out = nullptr, double * heights_out = nullptr)
     {
       const size_t nx = (size_t)(nq_ + nv_), n = X.size() / nx, nr = 3 * (size_t)gn_, na = (size_t)(nv_ - 6);
       if (n == 0 || X.size() != n * nx || tau.size() != n * na)
@@ -396,7 +486,13 @@ namespace simple_mpc
       r.stops.dropped.resize(n);
       const double *pl = planes.empty() ? nullptr : planes.data(), *pm = mu.empty() ? nullptr : mu.data(), *pp = push.empty() ? nullptr : push.data(),
                    *l0 = lam0.empty() ? nullptr : lam0.data();
-      if (body)
+      if (terrain)
+        check(smpc_robot_sim_ground_terrain_dynamics(h_, (int)n, X.data(), tau.data(), dt, terrain, pm, pp, joint, &s, l0, &m,
+                                                     body && !body->empty() ? body->data() : nullptr, r.s.g.v_next.data(), r.s.g.a.data(), r.s.g.lambda.data(),
+                                                     r.s.lambda_contact.data(), r.s.g.gap.data(), r.s.g.contact.data(), r.s.sweeps.data(), r.s.residual.data(),
+                                                     r.tau_applied.data(), r.stops.stop_rows.data(), r.stops.lam_stop.data(), r.stops.dropped.data(), normals_out,
+                                                     heights_out));
+      else if (body)
         check(smpc_robot_sim_ground_body_dynamics(h_, (int)n, X.data(), tau.data(), dt, pl, pm, pp, joint, &s, l0, &m, body->empty() ? nullptr : body->data(),
                                                   r.s.g.v_next.data(), r.s.g.a.data(), r.s.g.lambda.data(), r.s.lambda_contact.data(), r.s.g.gap.data(),
                                                   r.s.g.contact.data(), r.s.sweeps.data(), r.s.residual.data(), r.tau_applied.data(), r.stops.stop_rows.data(),
@@ -483,5 +579,59 @@ namespace simple_mpc
         out[r * 10 + k] *= s;
     }
     return out;
+  }
+
+  // ---- host helpers for the terrain (plain C++, no GPU) ----
+  // the sampling of DESIGN 3.28 at the world point (x, y) of one tile heights [ny][nx] with node (0, 0) at (ox, oy): the height of the
+  // bilinear patch below the point (coordinates clamped to the grid; NaN and +-inf go to node 0) and its unit normal
+  struct TerrainSample
+  {
+    double h, n[3];
+  };
+  inline TerrainSample terrain_height(const std::vector<double> & heights, int nx, int ny, double cell, double ox, double oy, double x, double y)
+  {
+    if (nx < 2 || ny < 2 || heights.size() != (size_t)nx * (size_t)ny)
+      throw std::runtime_error("terrain_height: heights [ny][nx] with nx, ny >= 2 expected");
+    struct Cell
+    {
+      int i;
+      double u;
+    };
+    // (sim_terrain_cell and sim_terrain_sample of the library's smpc_sim_terrain_dims.h restated: this header ships without its sources)
+    auto cell_of = [&](double p, double o, int n) {
+      const double hi = (double)(n - 1), im = (double)(n - 2);
+      const double c = (p - o) / cell;
+      const double lo = c > 0.0 ? c : 0.0;
+      const double cl = lo < hi ? lo : hi;
+      const double xc = (c < 0.0 ? -c : c) <= 1.7976931348623157e308 ? cl : 0.0;
+      const double fl = std::floor(xc);
+      const double fi = fl < im ? fl : im;
+      return Cell{(int)fi, xc - fi};
+    };
+    const Cell a = cell_of(x, ox, nx), b = cell_of(y, oy, ny);
+    const double * H = heights.data() + (size_t)b.i * nx + a.i;
+    const double h00 = H[0], h10 = H[1], h01 = H[nx], h11 = H[nx + 1], u = a.u, v = b.u;
+    const double dx0 = h10 - h00, dx1 = h11 - h01, dy0 = h01 - h00;
+    const double h0 = h00 + u * dx0, h1 = h01 + u * dx1;
+    const double hx = (dx0 + v * (dx1 - dx0)) / cell, hy = (dy0 + u * ((h11 - h10) - dy0)) / cell;
+    const double s = 1.0 / std::sqrt(hx * hx + hy * hy + 1.0);
+    TerrainSample r;
+    r.h = h0 + v * (h1 - h0);
+    r.n[0] = (0.0 - hx) * s;
+    r.n[1] = (0.0 - hy) * s;
+    r.n[2] = s;
+    return r;
+  }
+  // heights [ny][nx] = f(x, y) at the nodes x = i cell, y = j cell
+  template <class F>
+  inline std::vector<double> terrain_from_function(F f, int nx, int ny, double cell)
+  {
+    if (nx < 2 || ny < 2 || !(cell > 0.0))
+      throw std::runtime_error("terrain_from_function: nx, ny >= 2 and cell > 0 expected");
+    std::vector<double> h((size_t)nx * (size_t)ny);
+    for (int j = 0; j < ny; j++)
+      for (int i = 0; i < nx; i++)
+        h[(size_t)j * nx + i] = f((double)i * cell, (double)j * cell);
+    return h;
   }
 } // namespace simple_mpc

@@ -802,6 +802,68 @@ int smpc_robot_sim_ground_body_dynamics(smpc_robot_sim * sim, int n, const doubl
                                         double * residual_out, double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out,
                                         int32_t * dropped_out);
 
+/* ---- per-robot height-field terrain under that ground (simple-mpc_amd/csrc/smpc_sim_ground_joint_rt.h: sim_ground_terrain_rt_body,
+ * DESIGN 3.28) ----
+ * Settings.  A terrain of a handle that has a ground: heights[T][ny][nx] doubles are world z at the grid nodes, row j along world y,
+ * column i along world x.  cell > 0 is the node spacing in metres, the same in x and y.  tile[B] (int32) says which of the T tiles robot i
+ * stands on; null means 0.  origin[B][2] is the world (x, y) of node (0, 0) of robot i's tile; null means (0, 0).  Tiles are shared: a
+ * thousand robots may stand on the same tile at different origins.
+ * Admission (host only, smpc_sim_terrain_dims.h; it answers before anything is allocated, names the field and the first offending index,
+ * and leaves the previous terrain in force): nx, ny >= 2 and T >= 1; T ny nx <= 4 194 304 nodes; every height is finite; cell is finite
+ * and positive; tile lies in [0, T); origin is finite; at each of the four corners of every cell hx^2 + hy^2 <= 3, which is the rule
+ * n.z >= 0.5 of DESIGN 3.24 (the gradient of a bilinear patch is extremal at its corners).
+ * Sampling.  For contact point c at p = p_c:
+ *   1 x = (p.x - o.x) / cell, clamped to [0, nx - 1]; i = min(floor(x), nx - 2), u = x - i.  The same in y gives j and v.
+ *   2 The clamping is done in double before any conversion to an integer; the selects are written so that a NaN or +-inf coordinate
+ *     yields index 0.  The tile index is clamped to [0, T - 1] in the kernel as well.  No value read from memory can index outside the
+ *     array.
+ *   3 With h00 = H[j][i], h10 = H[j][i+1], h01 = H[j+1][i], h11 = H[j+1][i+1]: dx0 = h10 - h00, dx1 = h11 - h01, dy0 = h01 - h00;
+ *     h0 = h00 + u dx0, h1 = h01 + u dx1, h = h0 + v (h1 - h0); hx = (dx0 + v (dx1 - dx0)) / cell, hy = (dy0 + u ((h11 - h10) - dy0)) / cell.
+ *   4 s = 1 / sqrt(hx hx + hy hy + 1), n_c = ((0 - hx) s, (0 - hy) s, s).
+ *   5 The frame t1, t2 of point c comes from n_c by the formula of DESIGN 3.24.
+ *   6 The gap is phi_c = n_c.z (p.z - h): the distance to the tangent plane of the terrain below the point.
+ * This order of operations is chosen so that a tile whose heights all equal ground_z gives n = (0, 0, 1), h = ground_z and the frame of
+ * the flat plane exactly.
+ * The step is the step of DESIGN 3.23 - 3.27 with n_c, t1_c, t2_c, phi_c in place of the robot's n, t1, t2, phi: in the rows of point c,
+ * in c0, and in lambda_world(c) = Rc_c lambda_c.  Unchanged: the sweep, erp, compliance, the per-robot mu and push of
+ * smpc_robot_sim_set_ground_env / smpc_robot_sim_set_push, the solver settings, the joint model, the stop rows and the body parameters.
+ * WHILE A TERRAIN IS SET THE `planes` OF smpc_robot_sim_set_ground_env ARE NOT READ.  The warm buffer stays "in the point's own contact
+ * frame", which now moves with the foot.  Vertical faces, contacts other than at the foot points and the free-flight entries do not know
+ * the terrain.
+ *   smpc_robot_sim_set_terrain   stores the settings (host arrays, copied); NULL clears.  Needs smpc_robot_sim_set_ground first;
+ *                            smpc_robot_sim_set_ground called afterwards DROPS the terrain.  Independent of smpc_robot_sim_set_joint_model,
+ *                            smpc_robot_sim_set_body_params and smpc_robot_sim_set_ground_solver, in any order.  While it is set
+ *                            smpc_robot_sim_step_ground_device launches sim_ground_terrain_rt_body with the handle's joint model and body
+ *                            parameters, or with the inert model and the table's bodies where those are unset; once cleared, the handle
+ *                            launches exactly what it launched before.  Joins the handle's stream first.
+ *   smpc_robot_sim_get_terrain   the handle-owned device pointers heights [T][ny][nx], tile [B], origin [B][2] and the dims (NULL / 0
+ *                            while unset).  A resident loop may rewrite the arrays on the shared stream, unvalidated: the clamps above keep
+ *                            every index inside the array whatever is written.
+ *   smpc_robot_sim_read_terrain_last / smpc_robot_sim_get_terrain_last   normals [B][points][3] and heights [B][points] of the last step
+ *                            (n_c and h of every contact point; zeros before the first step), as a host copy / as device pointers.
+ *   smpc_robot_sim_ground_terrain_dynamics   smpc_robot_sim_ground_body_dynamics with the terrain settings in place of `plane`
+ *                            (tile [n] and origin [n][2] here; `terrain` must not be NULL) and the two new outputs normals_out
+ *                            [n][points][3] and heights_out [n][points].  The handle's own terrain is neither read nor changed. */
+typedef struct smpc_terrain_settings
+{
+  int32_t nx, ny, tiles;
+  double cell;
+  const double * heights; /* [tiles][ny][nx] */
+  const int32_t * tile;   /* [B] (or [n]), NULL: 0 */
+  const double * origin;  /* [B][2] (or [n][2]), NULL: (0, 0) */
+} smpc_terrain_settings;
+int smpc_robot_sim_set_terrain(smpc_robot_sim * sim, const smpc_terrain_settings * terrain);
+int smpc_robot_sim_get_terrain(smpc_robot_sim * sim, double ** heights_device, int32_t ** tile_device, double ** origin_device, int32_t * nx, int32_t * ny,
+                               int32_t * tiles, double * cell);
+int smpc_robot_sim_read_terrain_last(smpc_robot_sim * sim, double * normals_out, double * heights_out);
+int smpc_robot_sim_get_terrain_last(smpc_robot_sim * sim, double ** normals_device, double ** heights_device);
+int smpc_robot_sim_ground_terrain_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const smpc_terrain_settings * terrain,
+                                           const double * mu, const double * push, int push_joint, const smpc_ground_solver_settings * settings,
+                                           const double * lambda0, const smpc_joint_model_settings * model, const double * body, double * v_next_out,
+                                           double * a_out, double * lambda_out, double * lambda_contact_out, double * gap_out, uint32_t * contact_out,
+                                           int32_t * sweeps_out, double * residual_out, double * tau_applied_out, int32_t * stop_rows_out,
+                                           double * lam_stop_out, int32_t * dropped_out, double * normals_out, double * heights_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ struct smpc_robot_sim // stand-alone simulator handle: a robot table and nothing
   std::unique_ptr<RobotSimGroundWs> gw;  // its solver settings, warm buffer and read-outs (destroyed before the ground it refers to)
   std::unique_ptr<RobotSimGroundJoint> gj; // its joint model and read-outs (destroyed before the ground it refers to)
   std::unique_ptr<RobotSimGroundBody> gb;  // its per-robot body parameters (destroyed before the ground it refers to)
+  std::unique_ptr<RobotSimGroundTerrain> gt; // its per-robot height-field terrain (destroyed before the ground it refers to)
   std::vector<double> q_lo, q_hi;        // the robot table's joint limits [nv - 6]: the joint model's defaults
   std::vector<double> body_tab;          // the robot table's mass | com | inertia rows [njoints][10]: what is read while no body parameters are set
 };
@@ -193,7 +194,8 @@ namespace
                                  const double * mu, const double * push, int push_joint, const smpc_ground_solver_settings * settings, const double * lambda0,
                                  const smpc_joint_model_settings * model, const double * body, double * v_next_out, double * a_out, double * lambda_out,
                                  double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out, double * residual_out,
-                                 double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out);
+                                 double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out,
+                                 const smpc_terrain_settings * terrain = nullptr, double * normals_out = nullptr, double * heights_out = nullptr);
 } // namespace
 
 extern "C"
@@ -1319,6 +1321,7 @@ extern "C"
       sim->gw.reset(); // (and so do the solver settings and the warm buffer)
       sim->gj.reset(); // (and the joint model)
       sim->gb.reset(); // (and the body parameters)
+      sim->gt.reset(); // (and the terrain)
       sim->g = std::move(g);
     });
   }
@@ -1338,6 +1341,13 @@ extern "C"
       return fail(SMPC_ERR_INVALID, "smpc_robot_sim_step_ground_device: no ground yet, call smpc_robot_sim_set_ground first");
     if (!(dt > 0.0) || !std::isfinite(dt))
       return fail(SMPC_ERR_INVALID, "dt must be positive");
+    if (sim->gt && sim->gt->active) // (a terrain has been set: sim_ground_terrain_rt_body with the joint model and the bodies if there are any, else the inert model and a null body)
+      return guarded([&] {
+        if (!sim->gj)
+          sim->gj.reset(new RobotSimGroundJoint(*sim->g)); // (its arrays stay null: nothing is allocated)
+        const SimTerrainDev view = sim->gt->view();
+        sim->gj->step_device(X_device, tau_device, dt, sim->ge.get(), sim->gw.get(), sim->gb && sim->gb->active ? sim->gb->body : nullptr, &view);
+      });
     if (sim->gb && sim->gb->active) // (body parameters have been set: sim_ground_body_rt_body with the joint model if there is one, else the inert one)
       return guarded([&] {
         if (!sim->gj)
@@ -1678,6 +1688,82 @@ extern "C"
                                       v_next_out, a_out, lambda_out, lambda_contact_out, gap_out, contact_out, sweeps_out, residual_out, tau_applied_out,
                                       stop_rows_out, lam_stop_out, dropped_out);
   }
+
+  // ---- per-robot height-field terrain (smpc_sim_ground_joint_rt.h: sim_ground_terrain_rt_body) ----
+  int smpc_robot_sim_set_terrain(smpc_robot_sim * sim, const smpc_terrain_settings * terrain)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_set_terrain: no ground yet, call smpc_robot_sim_set_ground first");
+    // admission before anything else: nothing is allocated, and the previous terrain stays
+    const std::string why = sim_terrain_admission_error(sim->e->B, terrain);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      if (!sim->gt)
+      {
+        if (!terrain) // (nothing to clear, nothing allocated)
+          return;
+        sim->gt.reset(new RobotSimGroundTerrain(*sim->g));
+      }
+      sim->gt->set(terrain);
+    });
+  }
+  int smpc_robot_sim_get_terrain(smpc_robot_sim * sim, double ** heights_device, int32_t ** tile_device, double ** origin_device, int32_t * nx, int32_t * ny,
+                                 int32_t * tiles, double * cell)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    const bool on = sim->gt && sim->gt->active;
+    if (heights_device)
+      *heights_device = on ? sim->gt->heights : nullptr;
+    if (tile_device)
+      *tile_device = on ? sim->gt->tile : nullptr;
+    if (origin_device)
+      *origin_device = on ? sim->gt->origin : nullptr;
+    if (nx)
+      *nx = on ? sim->gt->nx : 0;
+    if (ny)
+      *ny = on ? sim->gt->ny : 0;
+    if (tiles)
+      *tiles = on ? sim->gt->tiles : 0;
+    if (cell)
+      *cell = on ? sim->gt->cell : 0.0;
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_read_terrain_last(smpc_robot_sim * sim, double * normals_out, double * heights_out)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->gt || !sim->gt->active)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_read_terrain_last: no terrain, call smpc_robot_sim_set_terrain first");
+    return guarded([&] { sim->gt->read_last(normals_out, heights_out); });
+  }
+  int smpc_robot_sim_get_terrain_last(smpc_robot_sim * sim, double ** normals_device, double ** heights_device)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    const bool on = sim->gt && sim->gt->active;
+    if (normals_device)
+      *normals_device = on ? sim->gt->n_last : nullptr;
+    if (heights_device)
+      *heights_device = on ? sim->gt->h_last : nullptr;
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_ground_terrain_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const smpc_terrain_settings * terrain,
+                                             const double * mu, const double * push, int push_joint, const smpc_ground_solver_settings * settings,
+                                             const double * lambda0, const smpc_joint_model_settings * model, const double * body, double * v_next_out,
+                                             double * a_out, double * lambda_out, double * lambda_contact_out, double * gap_out, uint32_t * contact_out,
+                                             int32_t * sweeps_out, double * residual_out, double * tau_applied_out, int32_t * stop_rows_out,
+                                             double * lam_stop_out, int32_t * dropped_out, double * normals_out, double * heights_out)
+  {
+    if (!terrain)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_ground_terrain_dynamics: terrain is null");
+    return ground_joint_body_dynamics("smpc_robot_sim_ground_terrain_dynamics", sim, n, X, tau, dt, nullptr, mu, push, push_joint, settings, lambda0, model, body,
+                                      v_next_out, a_out, lambda_out, lambda_contact_out, gap_out, contact_out, sweeps_out, residual_out, tau_applied_out,
+                                      stop_rows_out, lam_stop_out, dropped_out, terrain, normals_out, heights_out);
+  }
 }
 
 namespace
@@ -1686,7 +1772,8 @@ namespace
                                  const double * mu, const double * push, int push_joint, const smpc_ground_solver_settings * settings, const double * lambda0,
                                  const smpc_joint_model_settings * model, const double * body, double * v_next_out, double * a_out, double * lambda_out,
                                  double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out, double * residual_out,
-                                 double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out)
+                                 double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out,
+                                 const smpc_terrain_settings * terrain, double * normals_out, double * heights_out)
   {
     if (!sim || !X || !tau)
       return fail(SMPC_ERR_INVALID, "null argument");
@@ -1707,11 +1794,20 @@ namespace
       why = sim_joint_admission_error(n, sim->e->sz.na, sim->q_lo.data(), sim->q_hi.data(), model);
     if (why.empty())
       why = sim_body_admission_error(n, sim->e->sz.nq - 6, body);
+    if (why.empty())
+      why = sim_terrain_admission_error(n, terrain);
     if (!why.empty())
       return fail(SMPC_ERR_INVALID, why);
     return guarded([&] {
       if (!sim->gj)
         sim->gj.reset(new RobotSimGroundJoint(*sim->g)); // (staging only: the handle's ground steps keep their kernel until the setter is called)
+      SimTerrainDev view;
+      if (terrain)
+      {
+        if (!sim->gt)
+          sim->gt.reset(new RobotSimGroundTerrain(*sim->g)); // (staging only, likewise: the handle's own terrain is neither read nor changed)
+        view = sim->gt->stage(n, terrain);
+      }
       const double * body_dev = nullptr;
       if (body)
       {
@@ -1721,7 +1817,9 @@ namespace
       }
       sim->gj->dynamics(n, X, tau, dt, plane, mu, push, push_joint, sim_ground_ws_resolve(st), lambda0, model, sim->q_lo.data(), sim->q_hi.data(),
                         v_next_out, a_out, lambda_out, lambda_contact_out, gap_out, contact_out, sweeps_out, residual_out, tau_applied_out, stop_rows_out,
-                        lam_stop_out, dropped_out, body_dev);
+                        lam_stop_out, dropped_out, body_dev, terrain ? &view : nullptr);
+      if (terrain)
+        sim->gt->read_staged(n, normals_out, heights_out);
     });
   }
 } // namespace

@@ -18,10 +18,17 @@
 // loads mass, com and inertia of body j of robot i from body[i][j][0..9] (global memory -> registers of lane j, in the walk's first phase)
 // instead of from the device table; every other instruction is shared, the LDS is the same, and sim_ground_joint_rt_body compiles to
 // what it compiled to before the flag existed.
+// PER-ROBOT HEIGHT-FIELD TERRAIN: sim_ground_terrain_rt_body<NROWS> is the same source compiled with BODY and TERRAIN = true.
+// Phase 0 also loads tile and origin of the robot; the point lanes of the phase that forms p_c sample the robot's tile below their point
+// (four 8-byte loads per lane, issued together: THE ONE GLOBAL LOAD OUTSIDE PHASE 0, which cannot move there because its address depends
+// on the forward kinematics) and form the point's own normal, frame and gap; phase 3 rotates each J entry and phase 7 each lambda by its
+// point's frame, and phase 7 stores n_c and h of every point.  The per-point frames overlay sc.fb, dead after the tree walk: the LDS and
+// its bounds are unchanged, and the four earlier entry points compile to what they compiled to before the flag existed.
 #pragma once
 #include "smpc_sim_ground_ws_rt.h"
 #include "smpc_sim_joint_dims.h"
 #include "smpc_sim_body_dims.h"
+#include "smpc_sim_terrain_dims.h"
 #include <vector>
 
 namespace smpc
@@ -55,11 +62,30 @@ namespace smpc
   static_assert(sizeof(IdQuantRtScratch) + sizeof(SimGroundJointLds<24>) <= 163840 / 3, "three blocks per compute unit");
   static_assert(sizeof(IdQuantRtScratch) + sizeof(SimGroundJointLds<32>) <= 163840 / 2, "two blocks per compute unit");
 
+  // the terrain of a launch: device arrays and the dims of smpc_terrain_settings, and the two read-outs
+  struct SimTerrainDev
+  {
+    const double * heights; // [tiles][ny][nx]
+    const int * tile;       // [n] or null: 0
+    const double * origin;  // [n][2] or null: (0, 0)
+    int nx, ny, tiles;
+    double cell;
+    double * n_out; // [n][points][3] or null
+    double * h_out; // [n][points] or null
+  };
+
   // The one body of the step.  BODY = false is sim_ground_joint_rt_body; BODY = true is sim_ground_body_rt_body: `body` is
   // [n][nj][10] doubles on the device, and the tree walk of robot `inst` takes mass, com and inertia of body j from row [inst][j] instead
   // of from the device table (a null `body` reads the table; nj is the clamped joint count of the device table).  Nothing else differs.
-  template <int NROWS, bool BODY>
-  SMPC_DEV void sim_ground_joint_rt_impl(const SimGroundJointArgs & ja, const double * body, int block)
+  // TERRAIN = true is sim_ground_terrain_rt_body: every contact point has its own normal, frame and gap, sampled from the
+  // robot's height-field tile below the point.  THE FOUR HEIGHT LOADS OF A POINT ARE THE ONE GLOBAL LOAD OUTSIDE PHASE 0, AND THEY CANNOT
+  // MOVE THERE: their address depends on the point's position, which is the forward kinematics of the tree walk.  Each point lane issues
+  // its four 8-byte loads together.  Every index is clamped in double before it becomes an integer (sim_terrain_cell), and the tile index
+  // is clamped here, so no value read from memory can index outside `heights`.  env[0], env[1], env[2] carry origin x, origin y and the
+  // tile of the robot (the plane is not read); the per-point frames t1 | t2 | n and the heights lie in sc.fb, which is dead once the tree
+  // walk has formed the bias forces: no LDS is added.  With TERRAIN = false `tr` is not read and the code is what it was.
+  template <int NROWS, bool BODY, bool TERRAIN>
+  SMPC_DEV void sim_ground_joint_rt_impl(const SimGroundJointArgs & ja, const double * body, const SimTerrainDev * tr, int block)
   {
     typedef IdQuantRtScratch SC;
     typedef SimGroundLds<NROWS> L;
@@ -75,6 +101,7 @@ namespace smpc
     const SimGroundArgs & ka = ea.g;
     const int inst = block;
     const IdRtDevModel & mi = *ka.model;
+    static_assert(!TERRAIN || 10 * NPM <= MAXJ * 6, "the per-point frames and heights overlay sc.fb");
     // (wave-uniform sizes from the device table and the arguments, clamped so that no value can index outside the LDS arrays)
     const int nj = mi.t.njoints < MAXJ ? (mi.t.njoints > 1 ? mi.t.njoints : 1) : MAXJ;
     const int nv = nj + 5, nq = nj + 6, nx = 2 * nj + 11, na = nv - 6;
@@ -118,7 +145,9 @@ namespace smpc
       {
         const int k = lane - (NT - NE);
         double val;
-        if (k < 4)
+        if (TERRAIN && k < 4) // origin x, origin y and the tile of the robot (an int32 is exact in a double; clamped where it is used)
+          val = k < 2 ? (tr->origin != nullptr ? tr->origin[(size_t)inst * 2 + k] : 0.0) : (k == 2 && tr->tile != nullptr ? (double)tr->tile[inst] : 0.0);
+        else if (k < 4)
           val = ea.plane != nullptr ? ea.plane[(size_t)inst * 4 + k] : (k == 2 ? 1.0 : (k == 3 ? ka.ground_z : 0.0));
         else if (k == 4)
           val = ea.mu != nullptr ? ea.mu[inst] : ka.mu;
@@ -175,10 +204,34 @@ namespace smpc
         {
           const int f = c / P, k = c % P, jf = sc.fj[f];
           p = ld3(&sc.footp[f * 3]) + ldm3(&sc.oR[jf * 9]) * mk3(ka.points[k][0], ka.points[k][1], ka.points[k][2]); // foot frame rotation = joint rotation
-          double acc = e.env[0] * p.x;
-          acc += e.env[1] * p.y;
-          acc += e.env[2] * p.z;
-          gap = acc - e.env[3];
+          if constexpr (TERRAIN)
+          {
+            const int tnx = tr->nx > 2 ? tr->nx : 2, tny = tr->ny > 2 ? tr->ny : 2, tlast = tr->tiles > 1 ? tr->tiles - 1 : 0;
+            const double td = e.env[2];
+            const int tl = td < (double)tlast ? (td > 0.0 ? (int)td : 0) : tlast;
+            const SimTerrainCell cx = sim_terrain_cell(p.x, e.env[0], tr->cell, tnx), cy = sim_terrain_cell(p.y, e.env[1], tr->cell, tny);
+            const double * H = tr->heights + ((size_t)tl * tny + cy.i) * tnx + cx.i;
+            const double h00 = H[0], h10 = H[1], h01 = H[tnx], h11 = H[tnx + 1]; // (the one global load outside phase 0)
+            const SimTerrainSample sm = sim_terrain_sample(h00, h10, h01, h11, cx.u, cy.u, tr->cell);
+            // t1 = (e_y x n) / |e_y x n|, t2 = n x t1 (sim_ground_env_frame), of this point's normal
+            const double n0 = sm.n[0], n1 = sm.n[1], n2 = sm.n[2];
+            const double fx = n2, fz = -n0;
+            const double inv = 1.0 / sqrt(fx * fx + fz * fz);
+            const V3 t1 = mk3(fx * inv, 0.0, fz * inv);
+            double * fr = &sc.fb[c * 9];
+            st3(fr, t1);
+            st3(fr + 3, mk3(n1 * t1.z - n2 * t1.y, n2 * t1.x - n0 * t1.z, n0 * t1.y - n1 * t1.x));
+            st3(fr + 6, mk3(n0, n1, n2));
+            sc.fb[9 * NPM + c] = sm.h;
+            gap = n2 * (p.z - sm.h);
+          }
+          else
+          {
+            double acc = e.env[0] * p.x;
+            acc += e.env[1] * p.y;
+            acc += e.env[2] * p.z;
+            gap = acc - e.env[3];
+          }
         }
         st3(&s.pc[c * 3], p);
         s.gap[c] = gap;
@@ -215,7 +268,7 @@ namespace smpc
         jm.cnt[0] = rows;
         jm.cnt[1] = dropped;
       }
-      if (lane == 62) // t1 = (e_y x n) / |e_y x n|, t2 = n x t1 (sim_ground_env_frame)
+      if (!TERRAIN && lane == 62) // t1 = (e_y x n) / |e_y x n|, t2 = n x t1 (sim_ground_env_frame)
       {
         const double n0 = e.env[0], n1 = e.env[1], n2 = e.env[2];
         const double cx = n2, cz = -n0;
@@ -248,15 +301,16 @@ namespace smpc
         {
           const SV Sk = ldsv(&sc.S[k * 6]);
           const V3 lin = Sk.l + cross(Sk.a, ld3(&s.pc[c * 3])); // velocity of the point under the unit twist of column k
-          double r0 = e.t1[0] * lin.x;
-          r0 += e.t1[1] * lin.y;
-          r0 += e.t1[2] * lin.z;
-          double r1 = e.t2[0] * lin.x;
-          r1 += e.t2[1] * lin.y;
-          r1 += e.t2[2] * lin.z;
-          double r2 = e.env[0] * lin.x;
-          r2 += e.env[1] * lin.y;
-          r2 += e.env[2] * lin.z;
+          const double *ft1 = TERRAIN ? &sc.fb[c * 9] : e.t1, *ft2 = TERRAIN ? &sc.fb[c * 9 + 3] : e.t2, *fn = TERRAIN ? &sc.fb[c * 9 + 6] : e.env;
+          double r0 = ft1[0] * lin.x;
+          r0 += ft1[1] * lin.y;
+          r0 += ft1[2] * lin.z;
+          double r1 = ft2[0] * lin.x;
+          r1 += ft2[1] * lin.y;
+          r1 += ft2[2] * lin.z;
+          double r2 = fn[0] * lin.x;
+          r2 += fn[1] * lin.y;
+          r2 += fn[2] * lin.z;
           s.J[(3 * c + 0) * LDM + k] = r0;
           s.J[(3 * c + 1) * LDM + k] = r1;
           s.J[(3 * c + 2) * LDM + k] = r2;
@@ -500,15 +554,22 @@ namespace smpc
       if (lane < nr)
       {
         const int c = lane / 3, i = lane % 3;
-        double wl = e.t1[i] * s.lam[3 * c];
-        wl += e.t2[i] * s.lam[3 * c + 1];
-        wl += e.env[i] * s.lam[3 * c + 2];
+        const double *ft1 = TERRAIN ? &sc.fb[c * 9] : e.t1, *ft2 = TERRAIN ? &sc.fb[c * 9 + 3] : e.t2, *fn = TERRAIN ? &sc.fb[c * 9 + 6] : e.env;
+        double wl = ft1[i] * s.lam[3 * c];
+        wl += ft2[i] * s.lam[3 * c + 1];
+        wl += fn[i] * s.lam[3 * c + 2];
         ka.lam_out[(size_t)inst * nr + lane] = wl;
+        if constexpr (TERRAIN)
+          if (tr->n_out != nullptr)
+            tr->n_out[(size_t)inst * nr + lane] = fn[i];
         if (wa.lamc_out != nullptr)
           wa.lamc_out[(size_t)inst * nr + lane] = s.lam[lane];
       }
       if (lane < npts && ka.gap_out != nullptr)
         ka.gap_out[(size_t)inst * npts + lane] = s.gap[lane];
+      if constexpr (TERRAIN)
+        if (lane < npts && tr->h_out != nullptr)
+          tr->h_out[(size_t)inst * npts + lane] = sc.fb[9 * NPM + lane];
       if (lane >= 32 && lane < 32 + NJ)
       {
         const int r = lane - 32;
@@ -542,7 +603,7 @@ namespace smpc
   template <int NROWS>
   SMPC_DEV void sim_ground_joint_rt_body(const SimGroundJointArgs & ja, int block)
   {
-    sim_ground_joint_rt_impl<NROWS, false>(ja, nullptr, block);
+    sim_ground_joint_rt_impl<NROWS, false, false>(ja, nullptr, nullptr, block);
   }
 
   // ---- per-robot body parameters: the same step with the masses, centres of mass and inertias of robot i from body[i] ----
@@ -556,7 +617,22 @@ namespace smpc
   template <int NROWS>
   SMPC_DEV void sim_ground_body_rt_body(const SimGroundBodyArgs & ba, int block)
   {
-    sim_ground_joint_rt_impl<NROWS, true>(ba.j, ba.body, block);
+    sim_ground_joint_rt_impl<NROWS, true, false>(ba.j, ba.body, nullptr, block);
+  }
+
+  // ---- per-robot height-field terrain: the same step with the normal, frame and gap of every contact point sampled from the
+  // robot's tile; the body pointer is null-checked as above (null reads the table) ----
+  struct SimGroundTerrainArgs
+  {
+    SimGroundBodyArgs b;
+    SimTerrainDev t;
+  };
+  // (no LDS of its own: the frames overlay an array of the tree walk, so the bounds asserted above hold unchanged)
+  // grid = n, 64 lanes
+  template <int NROWS>
+  SMPC_DEV void sim_ground_terrain_rt_body(const SimGroundTerrainArgs & ta, int block)
+  {
+    sim_ground_joint_rt_impl<NROWS, true, true>(ta.b.j, ta.b.body, &ta.t, block);
   }
 
   // ---- host: the joint model and the per-robot read-outs of one simulator handle's ground (a sibling of RobotSimGroundWs; the
@@ -679,10 +755,22 @@ namespace smpc
       sc = sim_joint_resolve(m);
       active = true;
     }
-    // `body` ([n][njoints][10] on the device) non-null: sim_ground_body_rt_body, else the kernel of DESIGN 3.26
-    void run(int n, const SimGroundJointArgs & ja, const double * body = nullptr)
+    // `terr` non-null: sim_ground_terrain_rt_body (a null `body` reads the table there); else `body` ([n][njoints][10] on the device)
+    // non-null: sim_ground_body_rt_body, else the kernel of DESIGN 3.26
+    void run(int n, const SimGroundJointArgs & ja, const double * body = nullptr, const SimTerrainDev * terr = nullptr)
     {
-      if (body != nullptr)
+      if (terr != nullptr)
+      {
+        SimGroundTerrainArgs ta;
+        ta.b.j = ja;
+        ta.b.body = body;
+        ta.t = *terr;
+        if (g.gz.inst == 12)
+          launch<SimGroundTerrainArgs, sim_ground_terrain_rt_body<24>, 64, 1, 0>(n, g.sim.stream, ta);
+        else
+          launch<SimGroundTerrainArgs, sim_ground_terrain_rt_body<32>, 64, 1, 0>(n, g.sim.stream, ta);
+      }
+      else if (body != nullptr)
       {
         SimGroundBodyArgs ba;
         ba.j = ja;
@@ -699,7 +787,8 @@ namespace smpc
     }
     // `env` and `ws` may be null or inactive: the handle's uniform ground, no push; `sweeps` sweeps from zero.  Before set_model every
     // array is null and stops = 0: the inert model (a handle with body parameters and no joint model steps through here).
-    void step_device(double * X_dev, const double * tau_dev, double dt, const RobotSimGroundEnv * env, RobotSimGroundWs * ws, const double * body = nullptr)
+    void step_device(double * X_dev, const double * tau_dev, double dt, const RobotSimGroundEnv * env, RobotSimGroundWs * ws, const double * body = nullptr,
+                     const SimTerrainDev * terr = nullptr)
     {
       RobotSimRt & sim = g.sim;
       set_device(sim.device_id);
@@ -738,7 +827,7 @@ namespace smpc
       ja.rows_out = rows;
       ja.lams_out = lams;
       ja.dropped_out = dropped;
-      run(sim.B, ja, body);
+      run(sim.B, ja, body, terr);
     }
     void read_last(double * tau_out, int * rows_out, double * lams_out, int * dropped_out)
     {
@@ -767,7 +856,8 @@ namespace smpc
     void dynamics(int n, const double * X, const double * tau, double dt, const double * plane_h, const double * mu_h, const double * push_h, int joint,
                   const SimGroundWsSettings & st, const double * lam0_h, const smpc_joint_model_settings * m, const double * tab_lo, const double * tab_hi,
                   double * v_out, double * a_out, double * lam_out, double * lamc_out, double * gap_out, unsigned * con_out, int * sweeps_out, double * resid_out,
-                  double * tau_applied_out, int * rows_out, double * lams_out, int * dropped_out, const double * body_dev = nullptr)
+                  double * tau_applied_out, int * rows_out, double * lams_out, int * dropped_out, const double * body_dev = nullptr,
+                  const SimTerrainDev * terr = nullptr)
     {
       if (n < 1)
         throw InvalidCall("n must be positive");
@@ -883,7 +973,7 @@ namespace smpc
       ja.rows_out = hRows;
       ja.lams_out = hLamS;
       ja.dropped_out = hDrop;
-      run(n, ja, body_dev);
+      run(n, ja, body_dev, terr);
       if (v_out)
         d2h(v_out, hV, (size_t)n * sz.nv * sizeof(double), stream);
       if (a_out)
@@ -973,6 +1063,183 @@ namespace smpc
       }
       h2d(hBody, rows, sim_body_bytes(n, njoints()), sim.stream);
       return hBody;
+    }
+  };
+
+  // ---- host: the per-robot height-field terrain of one simulator handle's ground (a sibling of RobotSimGroundBody, whose
+  // device view RobotSimGroundJoint::step_device and dynamics take).  `active` between set(settings) and set(null): while it is, the
+  // handle's ground steps launch sim_ground_terrain_rt_body.  The staging of the host-buffer solve never touches the handle's own arrays. ----
+  struct RobotSimGroundTerrain
+  {
+    RobotSimGround & g;
+    bool active = false;
+    int nx = 0, ny = 0, tiles = 0;
+    double cell = 0.0;
+    double * heights = nullptr; // [tiles][ny][nx]
+    int * tile = nullptr;       // [B]
+    double * origin = nullptr;  // [B][2]
+    double * n_last = nullptr;  // [B][points][3]
+    double * h_last = nullptr;  // [B][points]
+    // host-buffer form (n states): grown on demand
+    int cap = 0;
+    size_t hcap = 0;
+    double *sHeights = nullptr, *sOrigin = nullptr, *sN = nullptr, *sH = nullptr;
+    int * sTile = nullptr;
+
+    explicit RobotSimGroundTerrain(RobotSimGround & ground) : g(ground) {}
+    RobotSimGroundTerrain(const RobotSimGroundTerrain &) = delete;
+    RobotSimGroundTerrain & operator=(const RobotSimGroundTerrain &) = delete;
+    void free_staging()
+    {
+      dev_free(sHeights);
+      dev_free(sOrigin);
+      dev_free(sN);
+      dev_free(sH);
+      dev_free(sTile);
+      sHeights = sOrigin = sN = sH = nullptr;
+      sTile = nullptr;
+      cap = 0;
+      hcap = 0;
+    }
+    ~RobotSimGroundTerrain()
+    {
+      free_staging();
+      dev_free(heights);
+      dev_free(tile);
+      dev_free(origin);
+      dev_free(n_last);
+      dev_free(h_last);
+    }
+    // (the caller has run sim_terrain_admission_error) the settings to the device; null clears: the handle launches what it launched before
+    void set(const smpc_terrain_settings * t)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      sim.wait(); // (a step in flight still reads the arrays)
+      if (!t)
+      {
+        active = false;
+        return;
+      }
+      const int B = sim.B, npts = g.gz.npts;
+      const size_t hb = sim_terrain_height_bytes(t->tiles, t->ny, t->nx);
+      {
+        AllocScope scope; // (a failing allocation releases the ones before it; the old arrays stay until all have succeeded)
+        double * n_heights = (double *)dev_alloc(hb);
+        int * n_tile = tile ? nullptr : (int *)dev_alloc(sim_terrain_tile_bytes(B));
+        double * n_origin = origin ? nullptr : (double *)dev_alloc(sim_terrain_origin_bytes(B));
+        double * n_n = n_last ? nullptr : (double *)dev_alloc(sim_terrain_normal_bytes(B, npts));
+        double * n_h = h_last ? nullptr : (double *)dev_alloc(sim_terrain_hlast_bytes(B, npts));
+        scope.commit();
+        dev_free(heights);
+        heights = n_heights;
+        if (n_tile)
+          tile = n_tile;
+        if (n_origin)
+          origin = n_origin;
+        if (n_n)
+          n_last = n_n;
+        if (n_h)
+          h_last = n_h;
+      }
+      std::vector<int> ht((size_t)B, 0);
+      std::vector<double> ho((size_t)B * 2, 0.0);
+      if (t->tile)
+        ht.assign(t->tile, t->tile + B);
+      if (t->origin)
+        ho.assign(t->origin, t->origin + (size_t)B * 2);
+      h2d(heights, t->heights, hb, sim.stream);
+      h2d(tile, ht.data(), sim_terrain_tile_bytes(B), sim.stream);
+      h2d(origin, ho.data(), sim_terrain_origin_bytes(B), sim.stream);
+      dev_zero(n_last, sim_terrain_normal_bytes(B, npts), sim.stream);
+      dev_zero(h_last, sim_terrain_hlast_bytes(B, npts), sim.stream);
+      stream_sync(sim.stream);
+      nx = t->nx;
+      ny = t->ny;
+      tiles = t->tiles;
+      cell = t->cell;
+      active = true;
+    }
+    // the device view of the handle's terrain for a step
+    SimTerrainDev view() const
+    {
+      SimTerrainDev d;
+      d.heights = heights;
+      d.tile = tile;
+      d.origin = origin;
+      d.nx = nx;
+      d.ny = ny;
+      d.tiles = tiles;
+      d.cell = cell;
+      d.n_out = n_last;
+      d.h_out = h_last;
+      return d;
+    }
+    void read_last(double * normals_out, double * heights_out)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      if (normals_out)
+        d2h(normals_out, n_last, sim_terrain_normal_bytes(sim.B, g.gz.npts), sim.stream);
+      if (heights_out)
+        d2h(heights_out, h_last, sim_terrain_hlast_bytes(sim.B, g.gz.npts), sim.stream);
+      stream_sync(sim.stream);
+    }
+    // the settings of a host-buffer solve of n states to the staging arrays, on the handle's stream; the device view for RobotSimGroundJoint::dynamics
+    SimTerrainDev stage(int n, const smpc_terrain_settings * t)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      const int npts = g.gz.npts;
+      const size_t hb = sim_terrain_height_bytes(t->tiles, t->ny, t->nx);
+      if (n > cap || hb > hcap)
+      {
+        stream_sync(sim.stream);
+        const int ncap = n > cap ? n : cap;
+        const size_t nh = hb > hcap ? hb : hcap;
+        free_staging();
+        try
+        {
+          sHeights = (double *)dev_alloc(nh);
+          sTile = (int *)dev_alloc(sim_terrain_tile_bytes(ncap));
+          sOrigin = (double *)dev_alloc(sim_terrain_origin_bytes(ncap));
+          sN = (double *)dev_alloc(sim_terrain_normal_bytes(ncap, npts));
+          sH = (double *)dev_alloc(sim_terrain_hlast_bytes(ncap, npts));
+        }
+        catch (...)
+        {
+          free_staging();
+          throw;
+        }
+        cap = ncap;
+        hcap = nh;
+      }
+      h2d(sHeights, t->heights, hb, sim.stream);
+      if (t->tile)
+        h2d(sTile, t->tile, sim_terrain_tile_bytes(n), sim.stream);
+      if (t->origin)
+        h2d(sOrigin, t->origin, sim_terrain_origin_bytes(n), sim.stream);
+      SimTerrainDev d;
+      d.heights = sHeights;
+      d.tile = t->tile ? sTile : nullptr;
+      d.origin = t->origin ? sOrigin : nullptr;
+      d.nx = t->nx;
+      d.ny = t->ny;
+      d.tiles = t->tiles;
+      d.cell = t->cell;
+      d.n_out = sN;
+      d.h_out = sH;
+      return d;
+    }
+    // (after the solve) the two read-outs of the staging arrays
+    void read_staged(int n, double * normals_out, double * heights_out)
+    {
+      RobotSimRt & sim = g.sim;
+      if (normals_out)
+        d2h(normals_out, sN, sim_terrain_normal_bytes(n, g.gz.npts), sim.stream);
+      if (heights_out)
+        d2h(heights_out, sH, sim_terrain_hlast_bytes(n, g.gz.npts), sim.stream);
+      stream_sync(sim.stream);
     }
   };
 } // namespace smpc

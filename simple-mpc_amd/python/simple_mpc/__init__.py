@@ -17,7 +17,7 @@ import numpy as np
 from . import _capi
 from ._capi import IdSettingsC, CentroidalSettingsC, FullDynamicsSettingsC, KinodynamicsSettingsC, MpcSettingsC, RobotModelC, SmpcLib, default_lib
 
-__all__ = ["load_robot", "robot_from_table", "RobotModelC", "RobotModelHandler", "RobotDataHandler", "KinodynamicsOCP", "CentroidalOCP", "FullDynamicsOCP", "MPC", "BatchedMPC", "Interpolator", "FrictionCompensation", "KinodynamicsID", "CentroidalID", "BatchedRobotSim", "centroidal_dynamics", "body_params", "scale_bodies", "add_payload"]
+__all__ = ["load_robot", "robot_from_table", "RobotModelC", "RobotModelHandler", "RobotDataHandler", "KinodynamicsOCP", "CentroidalOCP", "FullDynamicsOCP", "MPC", "BatchedMPC", "Interpolator", "FrictionCompensation", "KinodynamicsID", "CentroidalID", "BatchedRobotSim", "centroidal_dynamics", "body_params", "scale_bodies", "add_payload", "terrain_height", "terrain_from_function", "terrain_rough", "terrain_stairs"]
 
 
 def load_robot(name, lib=None):
@@ -108,6 +108,94 @@ def add_payload(body, joint, mass, position, inertia=None):
     out[..., j, 1:4] = cn
     out[..., j, 4:10] = np.stack([In[..., 0, 0], In[..., 0, 1], In[..., 1, 1], In[..., 0, 2], In[..., 1, 2], In[..., 2, 2]], -1)
     return out
+
+
+# ---- height-field terrain of BatchedRobotSim.setTerrain: plain numpy, no GPU.  heights [ny, nx] (or [T, ny, nx]) are world
+# z at the grid nodes, row j along world y, column i along world x, `cell` metres apart, node (0, 0) at `origin` ----
+def _terrain_cell(p, o, cell, n):
+    """sim_terrain_cell of smpc_sim_terrain_dims.h: (i, u) with the clamp in double and NaN / +-inf going to 0."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        x = (np.asarray(p, dtype=np.float64) - o) / cell
+        lo = np.where(x > 0.0, x, 0.0)
+        cl = np.where(lo < n - 1.0, lo, n - 1.0)
+        xc = np.where(np.abs(x) <= 1.7976931348623157e308, cl, 0.0)
+    fl = np.floor(xc)
+    fi = np.where(fl < n - 2.0, fl, n - 2.0)
+    return fi.astype(np.int64), xc - fi
+
+
+def terrain_height(heights, cell, origin, xy):
+    """The sampling of DESIGN 3.28 at the world points xy [..., 2] of one tile heights [ny, nx] with node (0, 0) at origin [2]: (h [...],
+    n [..., 3]), the height of the bilinear patch below the point (coordinates clamped to the grid) and its unit normal."""
+    H = np.asarray(heights, dtype=np.float64)
+    if H.ndim != 2 or H.shape[0] < 2 or H.shape[1] < 2:
+        raise RuntimeError("heights [ny, nx] with nx, ny >= 2 expected")
+    xy = np.asarray(xy, dtype=np.float64)
+    origin = np.asarray(origin, dtype=np.float64)
+    if xy.shape[-1:] != (2,) or origin.shape != (2,):
+        raise RuntimeError("xy [..., 2] and origin [2] expected")
+    cell = float(cell)
+    ny, nx = H.shape
+    i, u = _terrain_cell(xy[..., 0], origin[0], cell, nx)
+    j, v = _terrain_cell(xy[..., 1], origin[1], cell, ny)
+    h00, h10, h01, h11 = H[j, i], H[j, i + 1], H[j + 1, i], H[j + 1, i + 1]
+    dx0, dx1, dy0 = h10 - h00, h11 - h01, h01 - h00
+    h0, h1 = h00 + u * dx0, h01 + u * dx1
+    h = h0 + v * (h1 - h0)
+    hx = (dx0 + v * (dx1 - dx0)) / cell
+    hy = (dy0 + u * ((h11 - h10) - dy0)) / cell
+    s = 1.0 / np.sqrt(hx * hx + hy * hy + 1.0)
+    return h, np.stack([(0.0 - hx) * s, (0.0 - hy) * s, s], -1)
+
+
+def terrain_from_function(f, nx, ny, cell):
+    """heights [ny, nx] = f(x, y) at the nodes x = i cell, y = j cell (f takes two arrays [ny, nx] and returns one).  The tile is NOT
+    checked here: setTerrain refuses slopes above sqrt(3)."""
+    if nx < 2 or ny < 2 or not cell > 0.0:
+        raise RuntimeError("nx, ny >= 2 and cell > 0 expected")
+    x, y = np.meshgrid(np.arange(nx) * float(cell), np.arange(ny) * float(cell))
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(f(x, y), dtype=np.float64), (ny, nx)))
+
+
+def _terrain_limit(H, cell):
+    """H scaled down, if need be, so that |dh| between neighbouring nodes is at most 1.2 cell: hx^2 + hy^2 <= 2.88 <= 3 at every corner."""
+    d = max(float(np.abs(np.diff(H, axis=0)).max()), float(np.abs(np.diff(H, axis=1)).max()))
+    return H if d <= 1.2 * cell else H * (1.2 * cell / d)
+
+
+def terrain_rough(rng, nx, ny, cell, amplitude, wavelength):
+    """A rough tile heights [ny, nx] with zero mean: white noise from `rng` (a numpy Generator) smoothed by a Gaussian of standard
+    deviation wavelength / 4 (along y, then along x), scaled to a peak of `amplitude` metres; amplitude 0 gives exactly zeros.  It passes
+    admission by construction: if a height difference between neighbouring nodes exceeded 1.2 cell the tile is scaled down until none does."""
+    if nx < 2 or ny < 2 or not cell > 0.0 or not wavelength > 0.0 or amplitude < 0.0:
+        raise RuntimeError("nx, ny >= 2, cell > 0, wavelength > 0 and amplitude >= 0 expected")
+    w = rng.normal(size=(ny, nx))
+    sig = 0.25 * float(wavelength) / float(cell)
+    r = max(1, int(np.ceil(3.0 * sig)))
+    k = np.exp(-0.5 * (np.arange(-r, r + 1) / max(sig, 1e-12)) ** 2)
+    k /= k.sum()
+    for axis, n in ((0, ny), (1, nx)):
+        idx = np.clip(np.arange(-r, n + r), 0, n - 1)  # (edges repeated)
+        w = np.apply_along_axis(lambda a: np.convolve(a[idx], k, mode="valid"), axis, w)
+    w = w - w.mean()
+    peak = float(np.abs(w).max())
+    H = np.zeros((ny, nx)) if amplitude == 0.0 or peak == 0.0 else w * (float(amplitude) / peak)
+    return np.ascontiguousarray(_terrain_limit(H, float(cell)))
+
+
+def terrain_stairs(nx, ny, cell, rise, run, ramp):
+    """Stairs climbing along +x, heights [ny, nx]: tread k covers x in [k run, (k + 1) run) at height k rise, and each riser is a ramp over
+    the last `ramp` metres of its tread (there are no vertical faces in a height field).  It passes admission by construction: the ramp is
+    widened to at least one cell and to at least rise / 1.2."""
+    if nx < 2 or ny < 2 or not cell > 0.0 or not run > 0.0 or not ramp > 0.0:
+        raise RuntimeError("nx, ny >= 2, cell > 0, run > 0 and ramp > 0 expected")
+    ramp = min(float(run), max(float(ramp), float(cell), abs(float(rise)) / 1.2))
+    x = np.arange(nx) * float(cell)
+    k = np.floor(x / run)
+    t = x - k * run
+    h = rise * (k + np.clip((t - (run - ramp)) / ramp, 0.0, 1.0))
+    H = np.tile(h, (ny, 1))
+    return np.ascontiguousarray(_terrain_limit(H, float(cell)))
 
 
 class RobotModelHandler:
@@ -1948,7 +2036,7 @@ class BatchedRobotSim:
         return self._ground_joint_body(X, tau, dt, planes, mu, push, joint, lam0, warm_start, tol, min_sweeps,
                                        (tau_max, damping, armature, q_lo, q_hi, stops, activation, stop_erp), None, False)
 
-    def _ground_joint_body(self, X, tau, dt, planes, mu, push, joint, lam0, warm_start, tol, min_sweeps, model, body, with_body):
+    def _ground_joint_body(self, X, tau, dt, planes, mu, push, joint, lam0, warm_start, tol, min_sweeps, model, body, with_body, terrain=None):
         X = np.ascontiguousarray(np.array(X, dtype=np.float64))
         tau = np.ascontiguousarray(np.array(tau, dtype=np.float64))
         n = X.shape[0] if X.ndim == 2 else 0
@@ -1969,6 +2057,12 @@ class BatchedRobotSim:
         outs = (v.ctypes.data, a.ctypes.data, lam.ctypes.data, lamc.ctypes.data, gap.ctypes.data, con.ctypes.data, sw.ctypes.data, res.ctypes.data,
                 ta.ctypes.data, rows.ctypes.data, ls.ctypes.data, dr.ctypes.data)
         head = (self._h, n, X, tau, float(dt), p(pl), p(m), p(ps), int(joint), C.byref(s), p(l0), C.byref(jm))
+        if terrain is not None:
+            nrm, hts = np.zeros((n, npts, 3)), np.zeros((n, npts))
+            self._lib.check(self._lib.L.smpc_robot_sim_ground_terrain_dynamics(self._h, n, X, tau, float(dt), C.byref(terrain), p(m), p(ps), int(joint), C.byref(s),
+                                                                               p(l0), C.byref(jm), p(bd), *outs, nrm.ctypes.data, hts.ctypes.data))
+            return dict(v_next=v, a=a, lam=lam, gap=gap, contact=con, lam_contact=lamc, sweeps=sw, residual=res, tau_applied=ta, stop_rows=rows, lam_stop=ls,
+                        dropped=dr, normals=nrm, heights=hts)
         if with_body:
             self._lib.check(self._lib.L.smpc_robot_sim_ground_body_dynamics(*head, p(bd), *outs))
         else:
@@ -2005,6 +2099,71 @@ class BatchedRobotSim:
         parameters are neither read nor changed; n need not be the batch.  Returns the dict of groundJointDynamics."""
         return self._ground_joint_body(X, tau, dt, planes, mu, push, joint, lam0, warm_start, tol, min_sweeps,
                                        (tau_max, damping, armature, q_lo, q_hi, stops, activation, stop_erp), body, True)
+
+    # ---- per-robot height-field terrain (simple-mpc_amd/csrc/smpc_sim_ground_joint_rt.h: sim_ground_terrain_rt_body, DESIGN 3.28) ----
+    def _terrain_settings(self, n, heights, cell, tile, origin, who):
+        H = np.ascontiguousarray(np.array(heights, dtype=np.float64))
+        if H.ndim == 2:
+            H = H[None]
+        if H.ndim != 3:
+            raise RuntimeError("heights [T, ny, nx] (or [ny, nx]) expected")
+        tl = None
+        if tile is not None:
+            tl = np.ascontiguousarray(np.array(tile, dtype=np.int32))
+            if tl.shape != (n,):
+                raise RuntimeError("tile [%s] expected" % who)
+        og = self._env_array(origin, (n, 2), "origin [%s, 2]" % who)
+        p = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)
+        t = _capi.TerrainSettingsC(H.shape[2], H.shape[1], H.shape[0], float(cell), p(H), p(tl), p(og))
+        return t, (H, tl, og)
+
+    def setTerrain(self, heights=None, cell=0.0, tile=None, origin=None):
+        """Give every robot on the ground a height field to stand on: heights [T, ny, nx] (or one tile [ny, nx]) are world z at the grid
+        nodes, row j along world y, column i along world x, `cell` metres apart; tile [B] (int) says which tile robot i stands on (None:
+        0) and origin [B, 2] is the world (x, y) of node (0, 0) of its tile (None: (0, 0)).  Every contact point then has its own normal,
+        contact frame and gap, sampled from the bilinear patch below it (terrain_height() is the same sampling; outside the grid the
+        coordinates are clamped); mu, the push, the solver settings, the joint model and the body parameters are unchanged, and the planes
+        of setGroundEnv are not read while a terrain is set.  Refused: slopes with hx^2 + hy^2 > 3 at a cell corner.  heights = None
+        clears the terrain.  Needs setGround first; setGround called afterwards drops it."""
+        if heights is None:
+            self._lib.check(self._lib.L.smpc_robot_sim_set_terrain(self._h, None))
+            return
+        t, keep = self._terrain_settings(self.B, heights, cell, tile, origin, "B")
+        self._lib.check(self._lib.L.smpc_robot_sim_set_terrain(self._h, C.byref(t)))
+
+    def terrainDevicePointers(self):
+        """dict(heights, tile, origin (device pointers of the handle-owned [T][ny][nx] doubles, [B] int32 and [B][2] doubles; 0 while no
+        terrain is set), nx, ny, tiles, cell).  A resident loop may rewrite the arrays on the shared stream; values written there are not
+        validated, and the kernel's clamps keep every index inside the array.  The pointers change with every setTerrain."""
+        h, t, o = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nx, ny, nt, cell = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        self._lib.check(self._lib.L.smpc_robot_sim_get_terrain(self._h, C.byref(h), C.byref(t), C.byref(o), C.byref(nx), C.byref(ny), C.byref(nt), C.byref(cell)))
+        return dict(heights=int(h.value or 0), tile=int(t.value or 0), origin=int(o.value or 0), nx=nx.value, ny=ny.value, tiles=nt.value, cell=cell.value)
+
+    def lastTerrainNormals(self):
+        """The unit normal n_c of the terrain below every contact point at the last ground step [B, points, 3] (host copy)."""
+        out = np.zeros((self.B, self._ground_npts(), 3))
+        self._lib.check(self._lib.L.smpc_robot_sim_read_terrain_last(self._h, out.ctypes.data, None))
+        return out
+
+    def lastTerrainHeights(self):
+        """The terrain height h below every contact point at the last ground step [B, points] (host copy)."""
+        out = np.zeros((self.B, self._ground_npts()))
+        self._lib.check(self._lib.L.smpc_robot_sim_read_terrain_last(self._h, None, out.ctypes.data))
+        return out
+
+    def groundTerrainDynamics(self, X, tau, dt, heights, cell, tile=None, origin=None, mu=None, push=None, joint=0, lam0=None, warm_start=None, tol=0.0,
+                              min_sweeps=0, tau_max=None, damping=None, armature=None, q_lo=None, q_hi=None, stops=True, activation=0.0, stop_erp=0.0, body=None):
+        """groundBodyDynamics on a terrain instead of planes: heights [T, ny, nx] (or [ny, nx]), cell, tile [n], origin [n, 2] as in
+        setTerrain.  The handle's own terrain is neither read nor changed; n need not be the batch.  Returns the dict of
+        groundBodyDynamics and normals [n, points, 3], heights [n, points]."""
+        X = np.ascontiguousarray(np.array(X, dtype=np.float64))
+        n = X.shape[0] if X.ndim == 2 else 0
+        if n < 1:
+            raise RuntimeError("X [n, nq + nv], tau [n, nv - 6] expected")
+        t, keep = self._terrain_settings(n, heights, cell, tile, origin, "n")
+        return self._ground_joint_body(X, tau, dt, None, mu, push, joint, lam0, warm_start, tol, min_sweeps,
+                                       (tau_max, damping, armature, q_lo, q_hi, stops, activation, stop_erp), body, True, terrain=t)
 
 
 class FrictionCompensation:

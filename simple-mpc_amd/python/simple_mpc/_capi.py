@@ -180,6 +180,18 @@ class JointModelSettingsC(C.Structure):  # smpc_joint_model_settings
     ]
 
 
+class TerrainSettingsC(C.Structure):  # smpc_terrain_settings
+    _fields_ = [
+        ("nx", C.c_int32),
+        ("ny", C.c_int32),
+        ("tiles", C.c_int32),
+        ("cell", C.c_double),
+        ("heights", C.c_void_p),
+        ("tile", C.c_void_p),
+        ("origin", C.c_void_p),
+    ]
+
+
 # every symbol declared in include/smpc.h
 SYMBOLS = [
     "smpc_builtin_robot", "smpc_last_error", "smpc_device_count", "smpc_create", "smpc_create_centroidal", "smpc_create_fulldynamics", "smpc_get_contact_forces", "smpc_destroy", "smpc_get_dims",
@@ -199,6 +211,7 @@ SYMBOLS = [
     "smpc_robot_sim_read_ground_solver_last", "smpc_robot_sim_ground_solve_dynamics",
     "smpc_robot_sim_set_joint_model", "smpc_robot_sim_get_joint_last", "smpc_robot_sim_read_joint_last", "smpc_robot_sim_ground_joint_dynamics",
     "smpc_robot_sim_set_body_params", "smpc_robot_sim_read_body_params", "smpc_robot_sim_get_body_params", "smpc_robot_sim_ground_body_dynamics",
+    "smpc_robot_sim_set_terrain", "smpc_robot_sim_get_terrain", "smpc_robot_sim_read_terrain_last", "smpc_robot_sim_get_terrain_last", "smpc_robot_sim_ground_terrain_dynamics",
 ]
 
 
@@ -363,6 +376,14 @@ class SmpcLib:
         L.smpc_robot_sim_get_body_params.argtypes = [vp, C.POINTER(vp)]
         L.smpc_robot_sim_ground_body_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, vp, vp, vp, C.c_int, C.POINTER(GroundSolverSettingsC), vp,
                                                           C.POINTER(JointModelSettingsC), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.smpc_robot_sim_set_terrain.argtypes = [vp, C.POINTER(TerrainSettingsC)]
+        L.smpc_robot_sim_get_terrain.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_double)]
+        L.smpc_robot_sim_read_terrain_last.argtypes = [vp, vp, vp]
+        L.smpc_robot_sim_get_terrain_last.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.smpc_robot_sim_ground_terrain_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, C.POINTER(TerrainSettingsC), vp, vp, C.c_int,
+                                                             C.POINTER(GroundSolverSettingsC), vp, C.POINTER(JointModelSettingsC), vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                             vp, vp, vp, vp, vp, vp]
 
     def check(self, code):
         if code < 0:
