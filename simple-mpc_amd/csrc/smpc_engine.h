@@ -563,7 +563,9 @@ namespace smpc
       launch_trial(b, stage_args(b, slots, 1, D::LS_N - 1), KID_SELECT, true);
       this->launch_select(b, 1, D::LS_N - 1);
     }
-    size_t gains_stride() const override { return (size_t)std::max((int)D::G_STRIDE, (int)GainsK<D>::STRIDE); }
+    // the stride of the sweep in use, which every reader of the whole buffer indexes by (gains_out_body, pack_outputs_body, get_K);
+    // the allocation holds the larger of the two.  A part's view (slice) must start where those readers look for its first instance
+    size_t gains_stride() const override { return structured_riccati ? (size_t)GainsK<D>::STRIDE : (size_t)D::G_STRIDE; }
     void set_force_ref(StageShared<D> & s, int foot, double fz) const override { s.u_ref[3 * foot + 2] = fz; }
     bool parts_enabled() const override { return n_parts > 1 && B >= 64 * n_parts && !has_ext(buf); }
     // the parts' launches are issued alternately, so that every queue stays filled: the tail of one part's launch is filled by the next
