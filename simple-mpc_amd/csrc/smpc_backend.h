@@ -355,6 +355,20 @@ namespace smpc
     Body(a, (int)blockIdx.x);
   }
 
+  // blocks of launch<Args, Body, NT, MINW>() that one CU keeps resident (registers, LDS); 0: the runtime would not say
+#define SMPC_HAS_OCCUPANCY_QUERY 1
+  template <class Args, void (*Body)(const Args &, int), int NT, int MINW = 1>
+  inline int resident_blocks_per_cu()
+  {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel_entry<Args, Body, NT, MINW, 0>, NT, 0) != hipSuccess)
+    {
+      (void)hipGetLastError();
+      return 0;
+    }
+    return nb;
+  }
+
   template <class Args, void (*Body)(const Args &, int), int NT, int MINW = 1, int TAG = 0>
   inline void launch(int grid, stream_t s, const Args & a)
   {

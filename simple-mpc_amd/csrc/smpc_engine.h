@@ -222,6 +222,31 @@ namespace smpc
     int foot_joint_h[D::NF] = {0}; // (host copy for deriv2_commit_code)
     static constexpr int TRIAL_MINW = SMPC_TRIAL_MINW; // waves per SIMD the trial kernel's register budget allows
     static constexpr int RICCATI_MINW = 2;             // the Riccati sweep is latency bound: 2 waves per SIMD (8 per CU, 19.8 KB LDS each)
+    // Both sweeps as ONE staggered persistent launch (sweeps_kino_body): blocks of its grid, 0 = the two-launch form.
+    // One block per resident slot: (resident blocks per CU of the fused kernel) x (CUs of the device), unless the fused kernel keeps
+    // fewer blocks resident than the backward sweep alone -- then the handle stays with the two launches.  Read at handle creation:
+    // SMPC_FUSED_SWEEPS=0 forces the two-launch form, SMPC_FUSED_SWEEPS=1 the fused one, then with SMPC_SWEEP_SLOTS=n blocks if given.
+    int sweep_slots = 0;
+    // bit of the slot index that selects a slot's order (smpc_sweep_order.h); SMPC_SWEEP_STAGGER=n: an experiment switch, read with the others
+    int sweep_stagger = std::getenv("SMPC_SWEEP_STAGGER") ? std::min(std::max(std::atoi(std::getenv("SMPC_SWEEP_STAGGER")), 0), 30) : 0;
+    int fused_sweep_slots() const
+    {
+      const char * fs = std::getenv("SMPC_FUSED_SWEEPS");
+      const int want = fs ? std::atoi(fs) : -1;
+      if (!structured_riccati || want == 0)
+        return 0;
+      if (want == 1 && std::getenv("SMPC_SWEEP_SLOTS") && std::atoi(std::getenv("SMPC_SWEEP_SLOTS")) > 0)
+        return std::atoi(std::getenv("SMPC_SWEEP_SLOTS"));
+#ifdef SMPC_HAS_OCCUPANCY_QUERY
+      const int fused = resident_blocks_per_cu<SolverArgs<D>, sweeps_kino_body<D>, 64, RICCATI_MINW>();
+      const int alone = resident_blocks_per_cu<SolverArgs<D>, riccati_kino_body<D, false>, 64, RICCATI_MINW>();
+#else
+      const int fused = 8, alone = 8; // (a backend that runs the blocks one after the other has nothing to ask: the figures of the device)
+#endif
+      if (fused <= 0 || (want != 1 && fused < alone))
+        return 0;
+      return fused * dev_cu_count(device_id);
+    }
 
     KinoEngine(const smpc_robot_model * rm, const HostKinoSettings & ks, const HostMpcSettings & ms_, int batch, double gravity_arg, int device)
     : Base(KINO_KIND, ms_, batch, device)
@@ -364,6 +389,7 @@ namespace smpc
       buf.ls_sel = (int *)dev_alloc((size_t)B * sizeof(int));
       buf.und_list = (int *)dev_alloc((size_t)(B + 1) * sizeof(int));
       this->open_parts(std::getenv("SMPC_STREAMS") ? std::min(std::max(std::atoi(std::getenv("SMPC_STREAMS")), 1), (int)Base::MAX_PARTS) : 1);
+      sweep_slots = fused_sweep_slots();
       buf.stages = (StageShared<D> *)dev_alloc((size_t)H * sizeof(StageShared<D>));
       buf.model = (DevModel<D> *)dev_alloc(sizeof(DevModel<D>));
       X_dev = dalloc((size_t)B * D::NX);
@@ -531,6 +557,15 @@ namespace smpc
         {
           timed_launch<SolverArgs<D>, riccati_kino_body<D, true>, 64, RICCATI_MINW>(KID_RICCATI, b.B, solver_args(b));
           timed_launch<SolverArgs<D>, forward_kino_body<D, true>, 64>(KID_FORWARD, b.B, solver_args(b));
+        }
+        else if (sweep_slots > 0 && b.B > sweep_slots && !this->aux_launches && !parts_enabled())
+        {
+          // more instances than resident slots: one persistent launch walks both sweeps of every instance, the slots' orders staggered.
+          // Booked under the backward sweep's slot; the forward slot records no launch for it
+          SolverArgs<D> sa = solver_args(b);
+          sa.nslots = sweep_slots;
+          sa.stagger = sweep_stagger;
+          timed_launch<SolverArgs<D>, sweeps_kino_body<D>, 64, RICCATI_MINW>(KID_RICCATI, sweep_slots, sa);
         }
         else
         {

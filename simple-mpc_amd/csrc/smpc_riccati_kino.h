@@ -18,6 +18,7 @@
 //     accumulator layout of v_mfma_f64_16x16x4_f64 is the operand layout of the next product.
 #pragma once
 #include "smpc_solver_kernels.h"
+#include "smpc_sweep_order.h"
 #ifndef SMPC_KINO_RCP1
 #define SMPC_KINO_RCP1 false // (experiment switch: one Newton step on the pivot reciprocals of the kinodynamics sweep)
 #endif
@@ -350,9 +351,11 @@ namespace smpc
 
   // =============================================================================================
   // riccati_kino_body: grid = B, NT = 64 lanes (one wavefront per instance)
+  // riccati_kino_inst: the sweep of instance `inst` in the LDS block `s` -- what riccati_kino_body runs for its block and what
+  // sweeps_kino_body (below) runs for every instance of its slot's list
   // =============================================================================================
   template <class D, bool EXT = false> // EXT: optional constraint blocks present (see deriv_body)
-  SMPC_DEV void riccati_kino_body(const SolverArgs<D> & ka, int block)
+  SMPC_DEV void riccati_kino_inst(const SolverArgs<D> & ka, const int inst, RiccatiKinoLds<D> & s)
   {
     constexpr int NT = 64; // exactly one wavefront per workgroup: phases end with SMPC_LANES_END_WAVE
     constexpr int NDX = D::NDX, NU = D::NU, NV = D::NV, NA = D::NA, NF = D::NF, NXU = NDX + NU, NG = 12;
@@ -362,11 +365,8 @@ namespace smpc
     static_assert(2 * NDX + 1 <= 80 && NXU + 1 <= 64, "bordered matrices fit the 5x5 / 4x4 tile grids");
     const Buffers<D> & b = ka.b;
     const int H = b.H;
-    const int inst = block;
     // (kernel constants in scalar registers: as vector registers three of them were spilled in the prologue and reloaded in every stage)
     const double mu = SMPC_UNIFORM_F64(b.model->mu), imu = SMPC_UNIFORM_F64(1.0 / mu), dt = SMPC_UNIFORM_F64(b.model->dt), smu = SMPC_UNIFORM_F64(sqrt(mu));
-    SMPC_LDS(RiccatiKinoLds<D>, lds, 1);
-    RiccatiKinoLds<D> & s = lds[0];
     typedef RiccatiKinoLds<D> LD;
     double * const sP = s.w + LD::O_P;         // image of P (+ vector rows); sP[LD::O_Z] = 0
     double * const scr = s.w + LD::O_SCR;
@@ -398,7 +398,7 @@ namespace smpc
     SMPC_LANES_END_WAVE
 
 #ifdef SMPC_KINO_RICCATI_PROF
-    double * prof = (b.dbg != nullptr && block == 0) ? b.dbg : nullptr; // optional phase timers (block 0 only)
+    double * prof = (b.dbg != nullptr && inst == 0) ? b.dbg : nullptr; // optional phase timers (instance 0 only)
 #else
     // (phase timers: an experiment build, tools/variant_build.sh <name> -DSMPC_KINO_RICCATI_PROF -- their 63 uniform branches per stage cost 1 %)
     double * prof = nullptr;
@@ -1023,6 +1023,12 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
       prof_tick(prof, 13, tprev);
     }
   }
+  template <class D, bool EXT = false>
+  SMPC_DEV void riccati_kino_body(const SolverArgs<D> & ka, int block)
+  {
+    SMPC_LDS(RiccatiKinoLds<D>, lds, 1);
+    riccati_kino_inst<D, EXT>(ka, block, lds[0]);
+  }
 
   // =============================================================================================
   // forward_kino_body: grid = B, 64 lanes.  Forward sweep with the factored feedback + merit derivative.
@@ -1068,8 +1074,9 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
     double dx[NDX], du[NU], y[NDX], part[64], lpd_prev[NDX];
   };
 
+  // forward_kino_inst: the forward sweep of instance `inst` in the LDS block `s` (forward_kino_body for its block, sweeps_kino_body for its list)
   template <class D, bool EXT = false> // EXT: optional constraint blocks present (see deriv_body)
-  SMPC_DEV void forward_kino_body(const SolverArgs<D> & ka, int block)
+  SMPC_DEV void forward_kino_inst(const SolverArgs<D> & ka, const int inst, ForwardKinoLds<D> & s)
   {
     constexpr int NT = 64;
     constexpr int NDX = D::NDX, NU = D::NU, NC = D::NC, NV = D::NV, NA = D::NA, NF = D::NF;
@@ -1082,10 +1089,7 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
     constexpr int PER = FL::PER_LANE;
     const Buffers<D> & b = ka.b;
     const int H = b.H, R = b.R;
-    const int inst = block;
     const double mu = b.model->mu, dt = b.model->dt;
-    SMPC_LDS(FL, lds, 1);
-    FL & s = lds[0];
     SMPC_PLA(double, pf, NT, PER);
     // fetch stage t into the per-lane registers (flat staging index -> source chunk).  Chunk boundaries are
     // compile-time: for most n all 64 lanes fall into one chunk (plain base + lane address); the few straddling
@@ -1361,6 +1365,62 @@ wave_block_sweep<NT, 5, false, 0, NDX / 4, false, SMPC_KINO_RCP1>(t1, sw1, sw1 +
       b.ls_sel[inst] = -1;
     }
     SMPC_LANES_END_WAVE
+  }
+  template <class D, bool EXT = false>
+  SMPC_DEV void forward_kino_body(const SolverArgs<D> & ka, int block)
+  {
+    SMPC_LDS(ForwardKinoLds<D>, lds, 1);
+    forward_kino_inst<D, EXT>(ka, block, lds[0]);
+  }
+
+  // =============================================================================================
+  // sweeps_kino_body: both sweeps in one persistent launch, grid = ka.nslots blocks of 64 lanes (one block per resident slot of the
+  // backward sweep: 8 per CU).  Block s owns the instances s, s + nslots, s + 2 nslots, ... < B and walks them in an order fixed at
+  // launch (smpc_sweep_order.h): even s as  B F  per instance, odd s in pairs  B B F F  (a last unpaired one as B F) -- B = riccati_kino_inst, F =
+  // forward_kino_inst of the same instance, which needs that instance's gains only.  The orders are staggered so that about half of the
+  // resident waves are in the other phase: while one half streams gains (the forward sweep is HBM bound only when every wave of the chip
+  // is in it at once), the other half runs the matrix-core sweep (which is latency bound and slowed by a SIMD partner in the same phase).
+  // No block waits for another: no flags, no atomics; the only hand-over is a wave's own gains block, written by its lanes in B and read
+  // by its lanes in F.  One LDS block serves both phases.
+  // =============================================================================================
+  template <class D>
+  union SweepsKinoLds
+  {
+    RiccatiKinoLds<D> r;
+    ForwardKinoLds<D> f;
+  };
+  // phase boundary of sweeps_kino_body: every global store of the wave's lanes (gains of B, the step of F) has completed before any
+  // lane goes on, and everything the finished phase had in flight towards LDS has landed -- the wait that drains the wave's vector
+  // memory operations (loads and stores retire through one counter), then the wave's ordering point
+#define SMPC_SWEEPS_PHASE_END()                                                                                        \
+  do                                                                                                                   \
+  {                                                                                                                    \
+    SMPC_COPY_TO_LDS_WAIT();                                                                                           \
+    SMPC_WAVE_SYNC();                                                                                                  \
+  } while (0)
+  template <class D>
+  SMPC_DEV void sweeps_kino_body(const SolverArgs<D> & ka, int block)
+  {
+    SMPC_LDS(SweepsKinoLds<D>, lds, 1);
+    // one call site per phase: each per-instance function is inlined once
+    for (int k = 0;; k++)
+    {
+      // (the arguments are read again in every step, through an index the optimiser cannot see through, and the slot's list is formed
+      //  from them again: hoisted out of this loop, the argument pointers of BOTH phases would be live across each of them -- more
+      //  scalar registers than there are.  Only k lives across a phase.)
+      const SolverArgs<D> & kk = (&ka)[SMPC_UNIFORM_U32(SMPC_PIN(0))];
+      const int n = kk.nslots;
+      const int m = sweeps_slot_count(block, n, kk.b.B); // instances of this slot; its walk (smpc_sweep_order.h) has 2 m steps
+      if (k >= 2 * m)
+        break;
+      const SweepStep st = sweeps_slot_step(sweeps_slot_paired(block, kk.stagger), m, k);
+      const int inst = (int)SMPC_UNIFORM_U32(block + st.j * n);
+      if (!st.fwd)
+        riccati_kino_inst<D, false>(kk, inst, lds[0].r);
+      else
+        forward_kino_inst<D, false>(kk, inst, lds[SMPC_UNIFORM_U32(SMPC_PIN(0))].f); // (likewise: its LDS addresses are formed in its phase)
+      SMPC_SWEEPS_PHASE_END();
+    }
   }
 
   // K_t for (instance, stage) blocks: grid = B * nt, 64 lanes (lane = column of K)

@@ -25,6 +25,8 @@ namespace smpc
     // >= 0: SolverProxDDP::run's convergence test (reference src/mpc.cpp:43,212: TOL is the solver's tolerance): an instance whose
     // primal and dual infeasibilities are below it at the start of an iteration takes no step in that and the following iterations
     double stop_tol = -1.0;
+    int nslots = 0;  // sweeps_kino_body: blocks of its persistent grid (block s walks the instances s, s + nslots, ...)
+    int stagger = 0; // ... and the bit of s that says which of the two orders block s walks them in (smpc_sweep_order.h)
   };
 
   // out(i,j) = init(i,j) + sum_k X[k*ldx + i] * Y[k*ldy + j]  for an M x N output, register tiles TM x TN

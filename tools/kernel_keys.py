@@ -4,6 +4,7 @@ KEYS = {
     "deriv_body": ("10deriv_body", "DimsILi13ELi4EEE", 4096 * 51 * 64),
     "riccati_kino_body": ("riccati_kino_body", "", 4096 * 64),
     "forward_kino_body": ("forward_kino_body", "", 4096 * 64),
+    "sweeps_kino_body": ("sweeps_kino_body", "", 8 * 256 * 64),    # both sweeps in one persistent launch: a block per resident slot (8 per CU)
     "trial_body": ("10trial_body", "", 4096 * 51 * 64),
     "lane_tree_body": ("lane_tree_body", "ELb1ELb0E", 51 * 64 * 64),     # derivative pass: lane-per-problem tree pass, stream hand-over (64 problems per block)
     "lane_tree_ls_body": ("lane_tree_body", "ELb0ELb0E", 51 * 64 * 64),  # line search: the same kernel in evaluation mode (heads into tiles)
