@@ -435,7 +435,109 @@ namespace simple_mpc
       return r;
     }
 
+    // ---- body points and the touch mask (smpc_robot_sim_set_body_points and the entries after it) ----
+    // point k sits at offsets[k] (metres) in the frame of joint joints[k]; at most 16, shared by the batch; band in metres, 0 stands for 0.02
+    struct BodyPoints
+    {
+      std::vector<int32_t> joints;
+      std::vector<double> offsets; // [n][3]
+      double band = 0.0;
+    };
+    // A point whose gap to the ground (the robot's plane, or the terrain below the point) is under `band` takes one of the
+    // 8 - nfeet * points_per_foot free contact slots of the robot, in ascending k, and enters the contact solve as a foot point does.  With
+    // every point outside the band the results equal those without points bit for bit.  Needs setGround first; setGround called
+    // afterwards drops the points.  Independent of the terrain, the joint model, the body parameters, the environment and the solver settings.
+    void setBodyPoints(const BodyPoints & p)
+    {
+      const smpc_body_points_settings c = bodyPointsSettings(p);
+      check(smpc_robot_sim_set_body_points(h_, &c));
+    }
+    // the handle launches what it launched before setBodyPoints
+    void clearBodyPoints() { check(smpc_robot_sim_set_body_points(h_, nullptr)); }
+    struct BodyContacts
+    {
+      std::vector<int32_t> body_slots;   // [B][8]: k + 1 of the body point in slot s, 0: unused
+      std::vector<double> lam_body;      // [B][8][3]: forces on the robot in world axes
+      std::vector<double> body_gap;      // [B][16]: phi_k, 0 beyond the points
+      std::vector<int32_t> body_dropped; // [B]
+      std::vector<uint8_t> body_touch;   // [B]: 1 iff a slot carries a normal force
+    };
+    // the five read-outs of the last ground step (host copies; zeros while no points are set)
+    BodyContacts lastBodyContacts()
+    {
+      BodyContacts r = bodyContacts((size_t)batch_);
+      check(smpc_robot_sim_read_body_points_last(h_, r.body_slots.data(), r.lam_body.data(), r.body_gap.data(), r.body_dropped.data(), r.body_touch.data()));
+      return r;
+    }
+    // the handle-owned device arrays of the same (null while no points are set).  body_touch is the mask layout of
+    // smpc_reset_instances_device and resetGroundWarmStartDevice: handed to them on the shared stream it resets the robots that touched down
+    struct BodyPointsDevice
+    {
+      int32_t * body_slots = nullptr;
+      double *lam_body = nullptr, *body_gap = nullptr;
+      int32_t * body_dropped = nullptr;
+      uint8_t * body_touch = nullptr;
+    };
+    BodyPointsDevice bodyPointsDevicePointers()
+    {
+      BodyPointsDevice d;
+      check(smpc_robot_sim_get_body_points_last(h_, &d.body_slots, &d.lam_body, &d.body_gap, &d.body_dropped, &d.body_touch));
+      return d;
+    }
+    struct GroundPoints
+    {
+      GroundTerrain t; // (normals and heights are empty on the plane)
+      BodyContacts b;  // ([n] in place of [B])
+    };
+    // groundTerrainDynamics (terrain non-null) or groundBodyDynamics (null: the planes) with explicit body points; the handle's own points
+    // are neither read nor changed
+    GroundPoints groundPointsDynamics(const std::vector<double> & X, const std::vector<double> & tau, double dt, const BodyPoints & points,
+                                      const Terrain * terrain, const JointModel & model, const std::vector<double> & body = {},
+                                      const std::vector<double> & planes = {}, const std::vector<double> & mu = {}, const std::vector<double> & push = {},
+                                      int joint = 0, const std::vector<double> & lam0 = {}, bool warm_start = true, double tol = 0.0, int min_sweeps = 0)
+    {
+      const size_t n = X.size() / (size_t)(nq_ + nv_);
+      const smpc_body_points_settings pc = bodyPointsSettings(points);
+      smpc_terrain_settings c;
+      GroundPoints r;
+      if (terrain)
+      {
+        c = terrainSettings(*terrain, n);
+        r.t.normals.resize(n * (size_t)gn_ * 3);
+        r.t.heights.resize(n * (size_t)gn_);
+      }
+      r.b = bodyContacts(n);
+      r.t.j = groundJointBody(X, tau, dt, model, &body, planes, mu, push, joint, lam0, warm_start, tol, min_sweeps, terrain ? &c : nullptr,
+                              terrain ? r.t.normals.data() : nullptr, terrain ? r.t.heights.data() : nullptr, &pc, &r.b);
+      return r;
+    }
+
   private:
+    static BodyContacts bodyContacts(size_t n)
+    {
+      BodyContacts r;
+      r.body_slots.resize(n * 8);
+      r.lam_body.resize(n * 24);
+      r.body_gap.resize(n * 16);
+      r.body_dropped.resize(n);
+      r.body_touch.resize(n);
+      return r;
+    }
+    static smpc_body_points_settings bodyPointsSettings(const BodyPoints & p)
+    {
+      if (p.offsets.size() != p.joints.size() * 3)
+        throw std::runtime_error("joints [n] and offsets [n][3] expected");
+      smpc_body_points_settings c = {};
+      c.n = (int32_t)(p.joints.size() < 17 ? p.joints.size() : 17); // (a count above 16 is refused by the library, which names it)
+      for (size_t k = 0; k < p.joints.size() && k < 16; k++)
+      {
+        c.joint[k] = p.joints[k];
+        for (int i = 0; i < 3; i++)
+          c.offset[k][i] = p.offsets[k * 3 + i];
+      }
+      c.band = p.band;
+      return c;
+    }
     smpc_terrain_settings terrainSettings(const Terrain & t, size_t rows) const
     {
       if (t.nx < 0 || t.ny < 0 || t.tiles < 0 || t.heights.size() != (size_t)t.tiles * (size_t)t.ny * (size_t)t.nx)
@@ -457,7 +559,8 @@ namespace simple_mpc
     GroundJoint groundJointBody(const std::vector<double> & X, const std::vector<double> & tau, double dt, const JointModel & model,
                                 const std::vector<double> * body, const std::vector<double> & planes, const std::vector<double> & mu,
                                 const std::vector<double> & push, int joint, const std::vector<double> & lam0, bool warm_start, double tol, int min_sweeps,
-                                const smpc_terrain_settings * terrain = nullptr, double * normals_out = nullptr, double * heights_out = nullptr)
+                                const smpc_terrain_settings * terrain = nullptr, double * normals_out = nullptr, double * heights_out = nullptr,
+                                const smpc_body_points_settings * points = nullptr, BodyContacts * bc = nullptr)
     {
       const size_t nx = (size_t)(nq_ + nv_), n = X.size() / nx, nr = 3 * (size_t)gn_, na = (size_t)(nv_ - 6);
       if (n == 0 || X.size() != n * nx || tau.size() != n * na)
@@ -486,7 +589,14 @@ namespace simple_mpc
       r.stops.dropped.resize(n);
       const double *pl = planes.empty() ? nullptr : planes.data(), *pm = mu.empty() ? nullptr : mu.data(), *pp = push.empty() ? nullptr : push.data(),
                    *l0 = lam0.empty() ? nullptr : lam0.data();
-      if (terrain)
+      if (points)
+        check(smpc_robot_sim_ground_points_dynamics(h_, (int)n, X.data(), tau.data(), dt, terrain, pl, pm, pp, joint, &s, l0, &m,
+                                                    body && !body->empty() ? body->data() : nullptr, points, r.s.g.v_next.data(), r.s.g.a.data(),
+                                                    r.s.g.lambda.data(), r.s.lambda_contact.data(), r.s.g.gap.data(), r.s.g.contact.data(), r.s.sweeps.data(),
+                                                    r.s.residual.data(), r.tau_applied.data(), r.stops.stop_rows.data(), r.stops.lam_stop.data(),
+                                                    r.stops.dropped.data(), normals_out, heights_out, bc->body_slots.data(), bc->lam_body.data(),
+                                                    bc->body_gap.data(), bc->body_dropped.data(), bc->body_touch.data()));
+      else if (terrain)
         check(smpc_robot_sim_ground_terrain_dynamics(h_, (int)n, X.data(), tau.data(), dt, terrain, pm, pp, joint, &s, l0, &m,
                                                      body && !body->empty() ? body->data() : nullptr, r.s.g.v_next.data(), r.s.g.a.data(), r.s.g.lambda.data(),
                                                      r.s.lambda_contact.data(), r.s.g.gap.data(), r.s.g.contact.data(), r.s.sweeps.data(), r.s.residual.data(),
@@ -579,6 +689,21 @@ namespace simple_mpc
         out[r * 10 + k] *= s;
     }
     return out;
+  }
+
+  // ---- host helper for the body points (plain C++, no GPU): the eight corners of the box centre +- half_extents in the frame of `joint`,
+  // corner k at the signs (k & 1, k & 2, k & 4 -> x, y, z; 0 is the negative side) ----
+  inline BatchedRobotSim::BodyPoints box_points(int joint, const double centre[3], const double half_extents[3], double band = 0.0)
+  {
+    BatchedRobotSim::BodyPoints p;
+    p.band = band;
+    for (int k = 0; k < 8; k++)
+    {
+      p.joints.push_back(joint);
+      for (int i = 0; i < 3; i++)
+        p.offsets.push_back(centre[i] + (((k >> i) & 1) ? half_extents[i] : -half_extents[i]));
+    }
+    return p;
   }
 
   // ---- host helpers for the terrain (plain C++, no GPU) ----

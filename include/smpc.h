@@ -264,7 +264,8 @@ int smpc_load_state(smpc_handle * h, const void * buffer, size_t size);
  *                                 is built on the host and uploaded on the handle's stream, then as below
  *   smpc_reset_instances_device   re-applies src/mpc.cpp:72-89 to every instance with a non-zero byte in mask_device [B] (device memory):
  *                                 one kernel on the handle's stream, no host synchronisation -- a fall detector on the device writes the
- *                                 mask and nothing crosses the host.  The kernel reads the mask: it must stay valid until smpc_wait */
+ *                                 mask and nothing crosses the host.  The kernel reads the mask: it must stay valid until smpc_wait.
+ *                                 The detector this speaks of is body_touch of smpc_robot_sim_get_body_points_last (uint8_t [B]) */
 int smpc_reset_instances(smpc_handle * h, const int * instances, int n);
 int smpc_reset_instances_device(smpc_handle * h, const uint8_t * mask_device);
 /* xs_[t] of every instance into a dense device buffer [B][nx]; asynchronous on the handle's stream.
@@ -682,8 +683,9 @@ int smpc_robot_sim_ground_env_dynamics(smpc_robot_sim * sim, int n, const double
  *   smpc_robot_sim_reset_ground_warm_start   zeroes the warm rows of the n robots of a host list (unsorted, duplicates allowed; an index
  *                            outside 0 .. B - 1 refuses the whole call); n = 0 resets every robot.  Asynchronous on the handle's stream.
  *   smpc_robot_sim_reset_ground_warm_start_device   the same for every robot with a non-zero byte in mask_device [B] (device memory), one
- *                            kernel on the handle's stream, no host round trip.
- *   smpc_robot_sim_get_ground_solver_last   device pointers of sweeps_used [B], residual [B] and the warm buffer [B][3 points] (owned by the
+ *                            kernel on the handle's stream, no host round trip.  body_touch of smpc_robot_sim_get_body_points_last
+ *                            (uint8_t [B], written by the ground step itself) is a mask in this layout: the fall detector on the device.
+ *   smpc_robot_sim_get_ground_solver_last  device pointers of sweeps_used [B], residual [B] and the warm buffer [B][3 points] (owned by the
  *                            handle; they change when smpc_robot_sim_set_ground is called again; NULL before the setter or the first
  *                            smpc_robot_sim_ground_solve_dynamics: a getter allocates nothing); any output may be NULL.
  *   smpc_robot_sim_read_ground_solver_last  sweeps_used and residual of the last ground step copied to host buffers (either may be NULL);
@@ -863,6 +865,73 @@ int smpc_robot_sim_ground_terrain_dynamics(smpc_robot_sim * sim, int n, const do
                                            double * a_out, double * lambda_out, double * lambda_contact_out, double * gap_out, uint32_t * contact_out,
                                            int32_t * sweeps_out, double * residual_out, double * tau_applied_out, int32_t * stop_rows_out,
                                            double * lam_stop_out, int32_t * dropped_out, double * normals_out, double * heights_out);
+
+/* ---- body points: contact candidates on any link, and the touch mask (simple-mpc_amd/csrc/smpc_sim_ground_joint_rt.h:
+ * sim_ground_points_rt_body / sim_ground_points_terrain_rt_body) ----
+ * Settings.  A handle that has a ground gets BODY POINTS, shared by the batch: n in [0, 16] entries, joint[k] in [0, nj), offset[k][3]
+ *   (metres, in the frame of that joint), and band >= 0 (metres; 0 stands for 0.02).  n = 0 or a null pointer clears them.
+ * Slots.  The family's bound of 8 contact points (24 contact rows) per robot stays.  S = 8 - nfeet * points_per_foot slots are free beside
+ *   the foot points.  S = 0 is refused.
+ * One step of robot i (everything not named is as in DESIGN 3.23 - 3.28):
+ *   1 position    p_k = p_j + R_j o_k with j = joint[k], from the tree walk that places the feet.
+ *   2 gap         phi_k is the gap of a foot point at p_k.  Without a terrain: n . p_k - d with the robot's plane (setGroundEnv, else
+ *                 ground_z).  With a terrain: steps 1 - 6 of 3.28 at p_k, which also give the point its own n_k, t1_k, t2_k and h_k.
+ *   3 candidates  in ascending k: k is a candidate iff phi_k < band (so a NaN gap is none).  The first S candidates get the slots
+ *                 s = 0, 1, ... in that order; the others are counted in body_dropped.
+ *   4 rows        slot s is contact point c = nfeet P + s: three rows [t1 t2 n], exactly those of a foot point, at p_k, over the ancestors of
+ *                 joint[k], in the point's frame (the robot's plane frame, or its own on a terrain).  c0 gets phi_k / dt (phi_k >= 0) or
+ *                 erp phi_k / dt on the normal row.  The compliance and the robot's mu are the same.  The stop rows of 3.26 follow behind
+ *                 the last slot in use.
+ *   5 sweeps      each sweep runs the foot points in their order, then the slots in ascending s (normal row, the two tangential rows,
+ *                 projection onto the disc of radius mu lambda_n: the update of a foot point), then the stop rows.  Slot rows start from
+ *                 exactly 0 every step.  The warm buffer keeps its layout (foot rows only).  rho takes the slot rows too.  The stopping
+ *                 rule, min_sweeps and the kernel's 1 / (dt G_rr) deviation are unchanged.
+ *   6 outputs     per robot, besides those of 3.28 with their layouts unchanged:
+ *                   body_slots [8] int32     k + 1 of the candidate in slot s, 0 = unused
+ *                   lam_body [8][3]          forces ON the robot in world axes, 0 for unused slots
+ *                   body_gap [16]            phi_k for k < n, 0 beyond
+ *                   body_dropped             int32
+ *                   body_touch               uint8: 1 iff lambda_n > 0 in some slot, else 0
+ *                 Bit nfeet P + s of the contact word is the slot's lambda_n > 0.
+ *                 lastTerrainNormals / lastTerrainHeights keep the foot points only.
+ * With n = 0, or with every phi_k >= band, every added term is an exact zero and the shared outputs equal those of the kernel the handle
+ * launched before, bit for bit.
+ * Admission (host only, smpc_sim_points_dims.h; it answers before anything is allocated, names the field and the first offending index, and
+ * leaves the previous points in force).  A handle with body points always launches a 32-row kernel.  Not modelled: radii on the points, a
+ * friction coefficient of their own, more than 8 contact points per robot; the free-flight entries do not know the points.
+ *   smpc_robot_sim_set_body_points   stores the settings (copied); NULL or n = 0 clears, and the handle then launches exactly what it
+ *                            launched before.  Needs smpc_robot_sim_set_ground first; smpc_robot_sim_set_ground called afterwards DROPS
+ *                            the points.  Independent of the terrain, the joint model, the body parameters, the environment, the push and
+ *                            the solver settings, in any order.  Joins the handle's stream first.
+ *   smpc_robot_sim_get_body_points_last / smpc_robot_sim_read_body_points_last   the five outputs of the last step as device pointers
+ *                            (NULL while no points are set) / as host copies (joins the stream; zeros while no points are set):
+ *                            body_slots [B][8], lam_body [B][8][3], body_gap [B][16], body_dropped [B], body_touch [B].  body_touch is
+ *                            uint8_t [B], the mask layout smpc_reset_instances_device and smpc_robot_sim_reset_ground_warm_start_device
+ *                            read: handed to them on the shared stream it resets the robots that touched down, nothing crossing the host.
+ *   smpc_robot_sim_ground_points_dynamics   smpc_robot_sim_ground_terrain_dynamics with the points settings and the five outputs
+ *                            ([n] in place of [B]).  A NULL terrain means the plane (`plane` [n][4] or NULL as in
+ *                            smpc_robot_sim_ground_body_dynamics; not read with a terrain); normals_out / heights_out are written only
+ *                            with a terrain.  It neither reads nor changes the handle's points. */
+typedef struct smpc_body_points_settings
+{
+  int32_t n;
+  int32_t joint[16];
+  double offset[16][3];
+  double band;
+} smpc_body_points_settings;
+int smpc_robot_sim_set_body_points(smpc_robot_sim * sim, const smpc_body_points_settings * points);
+int smpc_robot_sim_get_body_points_last(smpc_robot_sim * sim, int32_t ** body_slots_device, double ** lam_body_device, double ** body_gap_device,
+                                        int32_t ** body_dropped_device, uint8_t ** body_touch_device);
+int smpc_robot_sim_read_body_points_last(smpc_robot_sim * sim, int32_t * body_slots_out, double * lam_body_out, double * body_gap_out,
+                                         int32_t * body_dropped_out, uint8_t * body_touch_out);
+int smpc_robot_sim_ground_points_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const smpc_terrain_settings * terrain,
+                                          const double * plane, const double * mu, const double * push, int push_joint,
+                                          const smpc_ground_solver_settings * settings, const double * lambda0, const smpc_joint_model_settings * model,
+                                          const double * body, const smpc_body_points_settings * points, double * v_next_out, double * a_out,
+                                          double * lambda_out, double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out,
+                                          double * residual_out, double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out,
+                                          int32_t * dropped_out, double * normals_out, double * heights_out, int32_t * body_slots_out,
+                                          double * lam_body_out, double * body_gap_out, int32_t * body_dropped_out, uint8_t * body_touch_out);
 
 #ifdef __cplusplus
 }

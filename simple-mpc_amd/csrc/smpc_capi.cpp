@@ -42,6 +42,7 @@ struct smpc_robot_sim // stand-alone simulator handle: a robot table and nothing
   std::unique_ptr<RobotSimGroundJoint> gj; // its joint model and read-outs (destroyed before the ground it refers to)
   std::unique_ptr<RobotSimGroundBody> gb;  // its per-robot body parameters (destroyed before the ground it refers to)
   std::unique_ptr<RobotSimGroundTerrain> gt; // its per-robot height-field terrain (destroyed before the ground it refers to)
+  std::unique_ptr<RobotSimGroundPoints> gp;  // its body points and their read-outs (destroyed before the ground it refers to)
   std::vector<double> q_lo, q_hi;        // the robot table's joint limits [nv - 6]: the joint model's defaults
   std::vector<double> body_tab;          // the robot table's mass | com | inertia rows [njoints][10]: what is read while no body parameters are set
 };
@@ -195,7 +196,24 @@ namespace
                                  const smpc_joint_model_settings * model, const double * body, double * v_next_out, double * a_out, double * lambda_out,
                                  double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out, double * residual_out,
                                  double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out,
-                                 const smpc_terrain_settings * terrain = nullptr, double * normals_out = nullptr, double * heights_out = nullptr);
+                                 const smpc_terrain_settings * terrain = nullptr, double * normals_out = nullptr, double * heights_out = nullptr,
+                                 const smpc_body_points_settings * points = nullptr, int32_t * body_slots_out = nullptr, double * lam_body_out = nullptr,
+                                 double * body_gap_out = nullptr, int32_t * body_dropped_out = nullptr, uint8_t * body_touch_out = nullptr);
+  // zeros in the five body-point read-outs of n robots (no points: nothing was launched for them)
+  void zero_body_points_outputs(int n, int32_t * body_slots_out, double * lam_body_out, double * body_gap_out, int32_t * body_dropped_out,
+                                uint8_t * body_touch_out)
+  {
+    if (body_slots_out)
+      std::memset(body_slots_out, 0, sim_points_slots_bytes(n));
+    if (lam_body_out)
+      std::memset(lam_body_out, 0, sim_points_lam_bytes(n));
+    if (body_gap_out)
+      std::memset(body_gap_out, 0, sim_points_gap_bytes(n));
+    if (body_dropped_out)
+      std::memset(body_dropped_out, 0, sim_points_dropped_bytes(n));
+    if (body_touch_out)
+      std::memset(body_touch_out, 0, sim_points_touch_bytes(n));
+  }
 } // namespace
 
 extern "C"
@@ -1322,6 +1340,7 @@ extern "C"
       sim->gj.reset(); // (and the joint model)
       sim->gb.reset(); // (and the body parameters)
       sim->gt.reset(); // (and the terrain)
+      sim->gp.reset(); // (and the body points)
       sim->g = std::move(g);
     });
   }
@@ -1341,6 +1360,18 @@ extern "C"
       return fail(SMPC_ERR_INVALID, "smpc_robot_sim_step_ground_device: no ground yet, call smpc_robot_sim_set_ground first");
     if (!(dt > 0.0) || !std::isfinite(dt))
       return fail(SMPC_ERR_INVALID, "dt must be positive");
+    if (sim->gp && sim->gp->active) // (body points have been set: a body-point kernel at 32 rows, on the terrain if there is one, with the joint model and the bodies if there are any)
+      return guarded([&] {
+        if (!sim->gj)
+          sim->gj.reset(new RobotSimGroundJoint(*sim->g)); // (its arrays stay null: nothing is allocated)
+        const bool terr = sim->gt && sim->gt->active;
+        SimTerrainDev view;
+        if (terr)
+          view = sim->gt->view();
+        const SimPointsDev pts = sim->gp->view();
+        sim->gj->step_device(X_device, tau_device, dt, sim->ge.get(), sim->gw.get(), sim->gb && sim->gb->active ? sim->gb->body : nullptr, terr ? &view : nullptr,
+                             &pts);
+      });
     if (sim->gt && sim->gt->active) // (a terrain has been set: sim_ground_terrain_rt_body with the joint model and the bodies if there are any, else the inert model and a null body)
       return guarded([&] {
         if (!sim->gj)
@@ -1764,6 +1795,74 @@ extern "C"
                                       v_next_out, a_out, lambda_out, lambda_contact_out, gap_out, contact_out, sweeps_out, residual_out, tau_applied_out,
                                       stop_rows_out, lam_stop_out, dropped_out, terrain, normals_out, heights_out);
   }
+
+  // ---- body points and the touch mask (smpc_sim_ground_joint_rt.h: sim_ground_points_rt_body / sim_ground_points_terrain_rt_body) ----
+  int smpc_robot_sim_set_body_points(smpc_robot_sim * sim, const smpc_body_points_settings * points)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_set_body_points: no ground yet, call smpc_robot_sim_set_ground first");
+    // admission before anything else: nothing is allocated, and the previous points stay
+    const std::string why = sim_points_admission_error(sim->e->sz.nfeet, sim->g->gz.P, sim->e->sz.nq - 6, points);
+    if (!why.empty())
+      return fail(SMPC_ERR_INVALID, why);
+    return guarded([&] {
+      if (!sim->gp)
+      {
+        if (!points || points->n == 0) // (nothing to clear, nothing allocated)
+          return;
+        sim->gp.reset(new RobotSimGroundPoints(*sim->g));
+      }
+      sim->gp->set(points);
+    });
+  }
+  int smpc_robot_sim_get_body_points_last(smpc_robot_sim * sim, int32_t ** body_slots_device, double ** lam_body_device, double ** body_gap_device,
+                                          int32_t ** body_dropped_device, uint8_t ** body_touch_device)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    const bool on = sim->gp && sim->gp->active;
+    if (body_slots_device)
+      *body_slots_device = on ? sim->gp->own.slots : nullptr;
+    if (lam_body_device)
+      *lam_body_device = on ? sim->gp->own.lam : nullptr;
+    if (body_gap_device)
+      *body_gap_device = on ? sim->gp->own.gap : nullptr;
+    if (body_dropped_device)
+      *body_dropped_device = on ? sim->gp->own.dropped : nullptr;
+    if (body_touch_device)
+      *body_touch_device = on ? sim->gp->own.touch : nullptr;
+    return SMPC_OK;
+  }
+  int smpc_robot_sim_read_body_points_last(smpc_robot_sim * sim, int32_t * body_slots_out, double * lam_body_out, double * body_gap_out,
+                                           int32_t * body_dropped_out, uint8_t * body_touch_out)
+  {
+    if (!sim)
+      return fail(SMPC_ERR_INVALID, "null argument");
+    if (!sim->g)
+      return fail(SMPC_ERR_INVALID, "smpc_robot_sim_read_body_points_last: no ground yet, call smpc_robot_sim_set_ground first");
+    if (!(sim->gp && sim->gp->active)) // (zeros while no points are set, without allocating)
+      return guarded([&] {
+        sim->e->wait();
+        zero_body_points_outputs(sim->e->B, body_slots_out, lam_body_out, body_gap_out, body_dropped_out, body_touch_out);
+      });
+    return guarded([&] { sim->gp->read_last(body_slots_out, lam_body_out, body_gap_out, body_dropped_out, body_touch_out); });
+  }
+  int smpc_robot_sim_ground_points_dynamics(smpc_robot_sim * sim, int n, const double * X, const double * tau, double dt, const smpc_terrain_settings * terrain,
+                                            const double * plane, const double * mu, const double * push, int push_joint,
+                                            const smpc_ground_solver_settings * settings, const double * lambda0, const smpc_joint_model_settings * model,
+                                            const double * body, const smpc_body_points_settings * points, double * v_next_out, double * a_out,
+                                            double * lambda_out, double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out,
+                                            double * residual_out, double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out,
+                                            int32_t * dropped_out, double * normals_out, double * heights_out, int32_t * body_slots_out,
+                                            double * lam_body_out, double * body_gap_out, int32_t * body_dropped_out, uint8_t * body_touch_out)
+  {
+    return ground_joint_body_dynamics("smpc_robot_sim_ground_points_dynamics", sim, n, X, tau, dt, terrain ? nullptr : plane, mu, push, push_joint, settings,
+                                      lambda0, model, body, v_next_out, a_out, lambda_out, lambda_contact_out, gap_out, contact_out, sweeps_out, residual_out,
+                                      tau_applied_out, stop_rows_out, lam_stop_out, dropped_out, terrain, normals_out, heights_out, points, body_slots_out,
+                                      lam_body_out, body_gap_out, body_dropped_out, body_touch_out);
+  }
 }
 
 namespace
@@ -1773,7 +1872,9 @@ namespace
                                  const smpc_joint_model_settings * model, const double * body, double * v_next_out, double * a_out, double * lambda_out,
                                  double * lambda_contact_out, double * gap_out, uint32_t * contact_out, int32_t * sweeps_out, double * residual_out,
                                  double * tau_applied_out, int32_t * stop_rows_out, double * lam_stop_out, int32_t * dropped_out,
-                                 const smpc_terrain_settings * terrain, double * normals_out, double * heights_out)
+                                 const smpc_terrain_settings * terrain, double * normals_out, double * heights_out,
+                                 const smpc_body_points_settings * points, int32_t * body_slots_out, double * lam_body_out, double * body_gap_out,
+                                 int32_t * body_dropped_out, uint8_t * body_touch_out)
   {
     if (!sim || !X || !tau)
       return fail(SMPC_ERR_INVALID, "null argument");
@@ -1796,8 +1897,11 @@ namespace
       why = sim_body_admission_error(n, sim->e->sz.nq - 6, body);
     if (why.empty())
       why = sim_terrain_admission_error(n, terrain);
+    if (why.empty())
+      why = sim_points_admission_error(sim->e->sz.nfeet, sim->g->gz.P, sim->e->sz.nq - 6, points);
     if (!why.empty())
       return fail(SMPC_ERR_INVALID, why);
+    const bool with_points = points != nullptr && points->n > 0;
     return guarded([&] {
       if (!sim->gj)
         sim->gj.reset(new RobotSimGroundJoint(*sim->g)); // (staging only: the handle's ground steps keep their kernel until the setter is called)
@@ -1815,11 +1919,22 @@ namespace
           sim->gb.reset(new RobotSimGroundBody(*sim->g)); // (staging only, likewise)
         body_dev = sim->gb->stage(n, body);
       }
+      SimPointsDev pview;
+      if (with_points)
+      {
+        if (!sim->gp)
+          sim->gp.reset(new RobotSimGroundPoints(*sim->g)); // (staging only, likewise: the handle's own points are neither read nor changed)
+        pview = sim->gp->stage(n, points);
+      }
       sim->gj->dynamics(n, X, tau, dt, plane, mu, push, push_joint, sim_ground_ws_resolve(st), lambda0, model, sim->q_lo.data(), sim->q_hi.data(),
                         v_next_out, a_out, lambda_out, lambda_contact_out, gap_out, contact_out, sweeps_out, residual_out, tau_applied_out, stop_rows_out,
-                        lam_stop_out, dropped_out, body_dev, terrain ? &view : nullptr);
+                        lam_stop_out, dropped_out, body_dev, terrain ? &view : nullptr, with_points ? &pview : nullptr);
       if (terrain)
         sim->gt->read_staged(n, normals_out, heights_out);
+      if (with_points)
+        sim->gp->read_staged(n, body_slots_out, lam_body_out, body_gap_out, body_dropped_out, body_touch_out);
+      else
+        zero_body_points_outputs(n, body_slots_out, lam_body_out, body_gap_out, body_dropped_out, body_touch_out);
     });
   }
 } // namespace

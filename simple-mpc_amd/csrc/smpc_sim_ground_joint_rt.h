@@ -24,11 +24,19 @@
 // on the forward kinematics) and form the point's own normal, frame and gap; phase 3 rotates each J entry and phase 7 each lambda by its
 // point's frame, and phase 7 stores n_c and h of every point.  The per-point frames overlay sc.fb, dead after the tree walk: the LDS and
 // its bounds are unchanged, and the four earlier entry points compile to what they compiled to before the flag existed.
+// BODY POINTS: sim_ground_points_rt_body<32> / sim_ground_points_terrain_rt_body<32> are the same source compiled with
+// POINTS = true (and BODY; TERRAIN for the second).  Phase 0 also loads joint and offset of body point k into the registers of lane k; the
+// phase that forms p_c places the points on lanes 0 .. 15 (gap against the plane, or a terrain sample of their own: four more height loads
+// on that lane, clamped as those of the feet), one lane then hands the candidates (phi_k < band, ascending k) the free slots behind the
+// foot points, and the candidate lanes write position, gap and frame of their slot.  From phase 3 on a slot is a contact point whose joint
+// is joint[k]; phase 7 stores body_slots, lam_body, body_gap, body_dropped and the touch byte.  The candidates' scratch lies in sc.fb
+// behind the per-point frames: no LDS is added, and the six earlier entry points compile to what they compiled to before the flag existed.
 #pragma once
 #include "smpc_sim_ground_ws_rt.h"
 #include "smpc_sim_joint_dims.h"
 #include "smpc_sim_body_dims.h"
 #include "smpc_sim_terrain_dims.h"
+#include "smpc_sim_points_dims.h"
 #include <vector>
 
 namespace smpc
@@ -74,6 +82,46 @@ namespace smpc
     double * h_out; // [n][points] or null
   };
 
+  // the body points of a launch: the device copy of smpc_body_points_settings with the band resolved, and the five read-outs
+  struct SimPointsDev
+  {
+    const int * joint;     // [16]
+    const double * offset; // [16][3]
+    int n;
+    double band;
+    int * slots_out;           // [n][8] or null
+    double * lam_out;          // [n][8][3] or null
+    double * gap_out;          // [n][16] or null
+    int * dropped_out;         // [n] or null
+    unsigned char * touch_out; // [n] or null
+  };
+
+  // phi, h, and the frame t1 | t2 | n of the terrain below p (steps 1 - 6 of DESIGN 3.28: the sampling of the foot points, for a body point)
+  struct SimPointSample
+  {
+    double phi, h, fr[9];
+  };
+  SMPC_DEV SimPointSample sim_points_terrain_sample(const SimTerrainDev * tr, const double ox, const double oy, const double td, const V3 p)
+  {
+    const int tnx = tr->nx > 2 ? tr->nx : 2, tny = tr->ny > 2 ? tr->ny : 2, tlast = tr->tiles > 1 ? tr->tiles - 1 : 0;
+    const int tl = td < (double)tlast ? (td > 0.0 ? (int)td : 0) : tlast;
+    const SimTerrainCell cx = sim_terrain_cell(p.x, ox, tr->cell, tnx), cy = sim_terrain_cell(p.y, oy, tr->cell, tny);
+    const double * H = tr->heights + ((size_t)tl * tny + cy.i) * tnx + cx.i;
+    const double h00 = H[0], h10 = H[1], h01 = H[tnx], h11 = H[tnx + 1]; // (the height loads of a body point, issued together)
+    const SimTerrainSample sm = sim_terrain_sample(h00, h10, h01, h11, cx.u, cy.u, tr->cell);
+    const double n0 = sm.n[0], n1 = sm.n[1], n2 = sm.n[2];
+    const double fx = n2, fz = -n0;
+    const double inv = 1.0 / sqrt(fx * fx + fz * fz);
+    const V3 t1 = mk3(fx * inv, 0.0, fz * inv);
+    SimPointSample r;
+    st3(r.fr, t1);
+    st3(r.fr + 3, mk3(n1 * t1.z - n2 * t1.y, n2 * t1.x - n0 * t1.z, n0 * t1.y - n1 * t1.x));
+    st3(r.fr + 6, mk3(n0, n1, n2));
+    r.h = sm.h;
+    r.phi = n2 * (p.z - sm.h);
+    return r;
+  }
+
   // The one body of the step.  BODY = false is sim_ground_joint_rt_body; BODY = true is sim_ground_body_rt_body: `body` is
   // [n][nj][10] doubles on the device, and the tree walk of robot `inst` takes mass, com and inertia of body j from row [inst][j] instead
   // of from the device table (a null `body` reads the table; nj is the clamped joint count of the device table).  Nothing else differs.
@@ -84,8 +132,11 @@ namespace smpc
   // is clamped here, so no value read from memory can index outside `heights`.  env[0], env[1], env[2] carry origin x, origin y and the
   // tile of the robot (the plane is not read); the per-point frames t1 | t2 | n and the heights lie in sc.fb, which is dead once the tree
   // walk has formed the bias forces: no LDS is added.  With TERRAIN = false `tr` is not read and the code is what it was.
-  template <int NROWS, bool BODY, bool TERRAIN>
-  SMPC_DEV void sim_ground_joint_rt_impl(const SimGroundJointArgs & ja, const double * body, const SimTerrainDev * tr, int block)
+  // POINTS = true (NROWS = 32 only) adds the body points of `bp`: their candidates take the contact points npts .. npts + nb - 1
+  // (the free slots), whose joint is joint[k] instead of fj[c / P].  sc.fb behind the frames holds, per body point, phi and its slot, and
+  // per slot its point and its joint (small integers, exact in a double).  With POINTS = false `bp` is not read and the code is what it was.
+  template <int NROWS, bool BODY, bool TERRAIN, bool POINTS>
+  SMPC_DEV void sim_ground_joint_rt_impl(const SimGroundJointArgs & ja, const double * body, const SimTerrainDev * tr, const SimPointsDev * bp, int block)
   {
     typedef IdQuantRtScratch SC;
     typedef SimGroundLds<NROWS> L;
@@ -102,6 +153,11 @@ namespace smpc
     const int inst = block;
     const IdRtDevModel & mi = *ka.model;
     static_assert(!TERRAIN || 10 * NPM <= MAXJ * 6, "the per-point frames and heights overlay sc.fb");
+    // sc.fb with body points: frames [9 NPM) | heights [NPM) | phi_k [16) | slot of k [16) | k of slot s [8) | joint of slot s [8) | slots in use, dropped
+    constexpr int NBP = SIM_POINTS_MAX, NBS = SIM_POINTS_SLOTS, FB_PHI = 10 * NPM, FB_SLOT = FB_PHI + NBP, FB_K = FB_SLOT + NBP, FB_J = FB_K + NBS,
+                  FB_CNT = FB_J + NBS;
+    static_assert(!POINTS || (NROWS == 32 && NPM == NBS && FB_CNT + 2 <= MAXJ * 6 && NBP <= 32 && 3 * NBS <= 32),
+                  "body points: the 32-row instantiation only; the candidates' scratch overlays sc.fb behind the frames; points on lanes 0 .. 15");
     // (wave-uniform sizes from the device table and the arguments, clamped so that no value can index outside the LDS arrays)
     const int nj = mi.t.njoints < MAXJ ? (mi.t.njoints > 1 ? mi.t.njoints : 1) : MAXJ;
     const int nv = nj + 5, nq = nj + 6, nx = 2 * nj + 11, na = nv - 6;
@@ -112,6 +168,11 @@ namespace smpc
     const int jpush = ea.push_joint < nj ? (ea.push_joint > 0 ? ea.push_joint : 0) : nj - 1;
     const double dt = ka.dt;
     const bool warm = wa.warm_start != 0 && wa.lam0 != nullptr;
+    // (body points: the count and the free slots are wave-uniform and clamped; the values of point k live in the registers of lane k)
+    const int nbp = POINTS ? (bp->n < NBP ? (bp->n > 0 ? bp->n : 0) : NBP) : 0;
+    const int smax = POINTS ? NPM - npts : 0;
+    SMPC_PL(int, bpj, NT);
+    SMPC_PLA(double, bpv, NT, 16); // offset 0..2 -> p_k 0..2 | phi 3 | h 4 | frame 5..13
     SMPC_LDS(SC, scs, 1);
     SMPC_LDS(LJ, ls, 1);
     SC & sc = scs[0];
@@ -164,6 +225,23 @@ namespace smpc
           val = fabs(v) <= 1.7976931348623157e308 ? v : 0.0;
         }
         s.lam[lane] = val;
+      }
+      if constexpr (POINTS)
+      {
+        const int k = lane < nbp ? lane : 0;
+        int j = 0;
+        double o0 = 0.0, o1 = 0.0, o2 = 0.0;
+        if (nbp > 0) // (wave-uniform; the pointers are read only then)
+        {
+          j = bp->joint[k];
+          o0 = bp->offset[k * 3];
+          o1 = bp->offset[k * 3 + 1];
+          o2 = bp->offset[k * 3 + 2];
+        }
+        SMPC_PLV(bpj) = j < nj ? (j > 0 ? j : 0) : nj - 1; // (clamped here as well: it indexes LDS)
+        SMPC_PLV(bpv)[0] = o0;
+        SMPC_PLV(bpv)[1] = o1;
+        SMPC_PLV(bpv)[2] = o2;
       }
     }
     SMPC_LANES_END_WAVE
@@ -236,6 +314,34 @@ namespace smpc
         st3(&s.pc[c * 3], p);
         s.gap[c] = gap;
       }
+      if constexpr (POINTS)
+        if (lane < nbp) // body point k on lane k: p_k = p_j + R_j o_k, its gap and, on a terrain, its own frame and height
+        {
+          const int j = SMPC_PLV(bpj);
+          const V3 p = ld3(&sc.op[j * 3]) + ldm3(&sc.oR[j * 9]) * mk3(SMPC_PLV(bpv)[0], SMPC_PLV(bpv)[1], SMPC_PLV(bpv)[2]);
+          double phi;
+          if constexpr (TERRAIN)
+          {
+            const SimPointSample sm = sim_points_terrain_sample(tr, e.env[0], e.env[1], e.env[2], p);
+            phi = sm.phi;
+            SMPC_PLV(bpv)[4] = sm.h;
+#pragma unroll
+            for (int i = 0; i < 9; i++)
+              SMPC_PLV(bpv)[5 + i] = sm.fr[i];
+          }
+          else
+          {
+            double acc = e.env[0] * p.x;
+            acc += e.env[1] * p.y;
+            acc += e.env[2] * p.z;
+            phi = acc - e.env[3];
+          }
+          SMPC_PLV(bpv)[0] = p.x;
+          SMPC_PLV(bpv)[1] = p.y;
+          SMPC_PLV(bpv)[2] = p.z;
+          SMPC_PLV(bpv)[3] = phi;
+          sc.fb[FB_PHI + lane] = phi;
+        }
       if (lane == 60) // stop candidates in ascending k: min(g-, g+) < activation; lower if g- <= g+
       {
         int rows = 0, dropped = 0;
@@ -285,18 +391,93 @@ namespace smpc
       }
     }
     SMPC_LANES_END_WAVE
-    // (wave-uniform: one wavefront owns one robot; clamped before it indexes LDS)
+    int nb_raw = 0, nb_drop = 0;
+    if constexpr (POINTS)
+    {
+      // one lane walks the body points in ascending k: phi_k < band (a NaN is none) takes the next free slot, the rest are counted
+      SMPC_LANES(NT)
+      if (lane == 61)
+      {
+        int used = 0, dropped = 0;
+        for (int k = 0; k < nbp; k++)
+        {
+          int slot = -1;
+          if (sc.fb[FB_PHI + k] < bp->band)
+          {
+            if (used < smax)
+            {
+              slot = used;
+              sc.fb[FB_K + used] = (double)k;
+              used++;
+            }
+            else
+              dropped++;
+          }
+          sc.fb[FB_SLOT + k] = (double)slot;
+        }
+        for (int r = used; r < NBS; r++)
+          sc.fb[FB_K + r] = 0.0;
+        sc.fb[FB_CNT] = (double)used;
+        sc.fb[FB_CNT + 1] = (double)dropped;
+      }
+      SMPC_LANES_END_WAVE
+      // the candidate lanes write their slot: contact point npts + slot
+      SMPC_LANES(NT)
+      {
+        if (lane >= 32 && lane < 32 + NBS)
+          sc.fb[FB_J + lane - 32] = 0.0;
+        if (lane < nbp)
+        {
+          const int slot = (int)sc.fb[FB_SLOT + lane];
+          if (slot >= 0 && slot < smax)
+          {
+            const int c = npts + slot;
+            st3(&s.pc[c * 3], mk3(SMPC_PLV(bpv)[0], SMPC_PLV(bpv)[1], SMPC_PLV(bpv)[2]));
+            s.gap[c] = SMPC_PLV(bpv)[3];
+            if constexpr (TERRAIN)
+            {
+#pragma unroll
+              for (int i = 0; i < 9; i++)
+                sc.fb[c * 9 + i] = SMPC_PLV(bpv)[5 + i];
+              sc.fb[9 * NPM + c] = SMPC_PLV(bpv)[4];
+            }
+          }
+        }
+      }
+      SMPC_LANES_END_WAVE
+      SMPC_LANES(NT)
+      if (lane < nbp)
+      {
+        const int slot = (int)sc.fb[FB_SLOT + lane];
+        if (slot >= 0 && slot < smax)
+          sc.fb[FB_J + slot] = (double)SMPC_PLV(bpj);
+      }
+      SMPC_LANES_END_WAVE
+      nb_raw = (int)SMPC_UNIFORM_U32((int)sc.fb[FB_CNT]);
+      nb_drop = (int)SMPC_UNIFORM_U32((int)sc.fb[FB_CNT + 1]);
+    }
+    // (wave-uniform: one wavefront owns one robot; clamped before it indexes anything)
+    const int nb = POINTS ? (nb_raw < smax ? (nb_raw > 0 ? nb_raw : 0) : (smax > 0 ? smax : 0)) : 0;
+    const int npt = npts + nb, nrp = 3 * npt; // contact points and rows with the slots in use (npts and nr without body points)
     const int ns_raw = (int)SMPC_UNIFORM_U32(jm.cnt[0]);
-    const int ns_max = NCM - nr < NJ ? NCM - nr : NJ;
+    const int ns_max = NCM - nrp < NJ ? NCM - nrp : NJ;
     const int ns = ns_raw < ns_max ? (ns_raw > 0 ? ns_raw : 0) : ns_max;
-    const int nrt = nr + ns;
+    const int nrt = nrp + ns;
     // ---- phase 3: the rows of every point, t1 t2 n in the contact frame; the stop rows behind them ----
     SMPC_LANES(NT)
     {
-      for (int idx = lane; idx < npts * nv; idx += NT)
+      for (int idx = lane; idx < npt * nv; idx += NT)
       {
         const int c = idx / nv, k = idx % nv;
-        const int jf = sc.fj[c / P], jk = k < 6 ? 0 : k - 5;
+        int jf;
+        if (POINTS && c >= npts) // (a slot: the joint of its body point, clamped again as it comes from LDS)
+        {
+          const int jb = (int)sc.fb[FB_J + c - npts];
+          jf = jb < nj ? (jb > 0 ? jb : 0) : nj - 1;
+        }
+        else
+          jf = sc.fj[c / P];
+        const int jk = k < 6 ? 0 : k - 5;
         if ((sc.anc[jf] >> jk) & 1u)
         {
           const SV Sk = ldsv(&sc.S[k * 6]);
@@ -320,7 +501,7 @@ namespace smpc
       {
         const int r = lane - 32;
         const int k = jm.sk[r] < na ? (jm.sk[r] > 0 ? jm.sk[r] : 0) : na - 1;
-        s.J[(nr + r) * LDM + 6 + k] = (double)jm.ss[r];
+        s.J[(nrp + r) * LDM + 6 + k] = (double)jm.ss[r];
       }
     }
     SMPC_LANES_END_WAVE
@@ -380,7 +561,7 @@ namespace smpc
       {
         const int r = lane - 32;
         double acc = 0.0;
-        if (r < nr)
+        if (r < nrp)
         {
           for (int k = 0; k < nv; k++)
             acc += s.J[r * LDM + k] * s.vf[k];
@@ -392,7 +573,7 @@ namespace smpc
         }
         else
         {
-          const int i = r - nr;
+          const int i = r - nrp;
           const int k = jm.sk[i] < na ? (jm.sk[i] > 0 ? jm.sk[i] : 0) : na - 1;
           acc = (double)jm.ss[i] * s.vf[6 + k] + jm.sg[i];
         }
@@ -424,7 +605,7 @@ namespace smpc
     SMPC_LANES_END_WAVE
     for (int sw = 0; sw < ka.sweeps; sw++)
     {
-      for (int c = 0; c < npts; c++)
+      for (int c = 0; c < npt; c++)
       {
         const int rn = 3 * c + 2;
         SMPC_LANES(NT)
@@ -472,7 +653,7 @@ namespace smpc
         }
         SMPC_LANES_END_WAVE
       }
-      for (int r = nr; r < nrt; r++) // the stop rows: the update of a normal row
+      for (int r = nrp; r < nrt; r++) // the stop rows: the update of a normal row
       {
         SMPC_LANES(NT)
         if (lane == 0)
@@ -576,15 +757,51 @@ namespace smpc
         if (ja.rows_out != nullptr)
           ja.rows_out[(size_t)inst * NJ + r] = r < ns ? jm.ss[r] * (jm.sk[r] + 1) : 0;
         if (ja.lams_out != nullptr)
-          ja.lams_out[(size_t)inst * NJ + r] = r < ns ? s.lam[nr + r] : 0.0;
+          ja.lams_out[(size_t)inst * NJ + r] = r < ns ? s.lam[nrp + r] : 0.0;
       }
       if (lane == 0)
       {
         unsigned word = 0u;
-        for (int c = 0; c < npts; c++)
+        for (int c = 0; c < npt; c++)
           if (s.lam[3 * c + 2] > 0.0)
             word |= 1u << c;
         ka.contact_out[inst] = word;
+      }
+      if constexpr (POINTS)
+      {
+        if (lane < 3 * NBS && bp->lam_out != nullptr) // lambda_world of slot lane / 3, 0 for a slot not in use
+        {
+          const int sl = lane / 3, i = lane % 3, c = npts + sl;
+          double wl = 0.0;
+          if (sl < nb)
+          {
+            const double *ft1 = TERRAIN ? &sc.fb[c * 9] : e.t1, *ft2 = TERRAIN ? &sc.fb[c * 9 + 3] : e.t2, *fn = TERRAIN ? &sc.fb[c * 9 + 6] : e.env;
+            wl = ft1[i] * s.lam[3 * c];
+            wl += ft2[i] * s.lam[3 * c + 1];
+            wl += fn[i] * s.lam[3 * c + 2];
+          }
+          bp->lam_out[(size_t)inst * 3 * NBS + lane] = wl;
+        }
+        if (lane >= 32 && lane < 32 + NBS && bp->slots_out != nullptr)
+        {
+          const int r = lane - 32;
+          bp->slots_out[(size_t)inst * NBS + r] = r < nb ? (int)sc.fb[FB_K + r] + 1 : 0;
+        }
+        if (lane >= 40 && lane < 40 + NBP && bp->gap_out != nullptr)
+        {
+          const int k = lane - 40;
+          bp->gap_out[(size_t)inst * NBP + k] = k < nbp ? sc.fb[FB_PHI + k] : 0.0;
+        }
+        if (lane == 3 && bp->dropped_out != nullptr)
+          bp->dropped_out[inst] = nb_drop + (nb_raw > nb ? nb_raw - nb : 0);
+        if (lane == 4 && bp->touch_out != nullptr)
+        {
+          unsigned char touch = 0;
+          for (int sl = 0; sl < nb; sl++)
+            if (s.lam[3 * (npts + sl) + 2] > 0.0)
+              touch = 1;
+          bp->touch_out[inst] = touch;
+        }
       }
       if (lane == 1)
       {
@@ -603,7 +820,7 @@ namespace smpc
   template <int NROWS>
   SMPC_DEV void sim_ground_joint_rt_body(const SimGroundJointArgs & ja, int block)
   {
-    sim_ground_joint_rt_impl<NROWS, false, false>(ja, nullptr, nullptr, block);
+    sim_ground_joint_rt_impl<NROWS, false, false, false>(ja, nullptr, nullptr, nullptr, block);
   }
 
   // ---- per-robot body parameters: the same step with the masses, centres of mass and inertias of robot i from body[i] ----
@@ -617,7 +834,7 @@ namespace smpc
   template <int NROWS>
   SMPC_DEV void sim_ground_body_rt_body(const SimGroundBodyArgs & ba, int block)
   {
-    sim_ground_joint_rt_impl<NROWS, true, false>(ba.j, ba.body, nullptr, block);
+    sim_ground_joint_rt_impl<NROWS, true, false, false>(ba.j, ba.body, nullptr, nullptr, block);
   }
 
   // ---- per-robot height-field terrain: the same step with the normal, frame and gap of every contact point sampled from the
@@ -632,7 +849,27 @@ namespace smpc
   template <int NROWS>
   SMPC_DEV void sim_ground_terrain_rt_body(const SimGroundTerrainArgs & ta, int block)
   {
-    sim_ground_joint_rt_impl<NROWS, true, true>(ta.b.j, ta.b.body, &ta.t, block);
+    sim_ground_joint_rt_impl<NROWS, true, true, false>(ta.b.j, ta.b.body, &ta.t, nullptr, block);
+  }
+
+  // ---- body points: the same step with contact candidates on any link in the free slots behind the foot points, and the
+  // touch byte; on the plane and on the terrain.  The body pointer is null-checked as above (null reads the table).  NROWS = 32 only. ----
+  struct SimGroundPointsArgs
+  {
+    SimGroundTerrainArgs t; // (t.t is not read on the plane)
+    SimPointsDev p;
+  };
+  // (no LDS of their own: the candidates' scratch overlays the same array of the tree walk, so the bounds asserted above hold unchanged)
+  // grid = n, 64 lanes
+  template <int NROWS>
+  SMPC_DEV void sim_ground_points_rt_body(const SimGroundPointsArgs & pa, int block)
+  {
+    sim_ground_joint_rt_impl<NROWS, true, false, true>(pa.t.b.j, pa.t.b.body, nullptr, &pa.p, block);
+  }
+  template <int NROWS>
+  SMPC_DEV void sim_ground_points_terrain_rt_body(const SimGroundPointsArgs & pa, int block)
+  {
+    sim_ground_joint_rt_impl<NROWS, true, true, true>(pa.t.b.j, pa.t.b.body, &pa.t.t, &pa.p, block);
   }
 
   // ---- host: the joint model and the per-robot read-outs of one simulator handle's ground (a sibling of RobotSimGroundWs; the
@@ -757,9 +994,22 @@ namespace smpc
     }
     // `terr` non-null: sim_ground_terrain_rt_body (a null `body` reads the table there); else `body` ([n][njoints][10] on the device)
     // non-null: sim_ground_body_rt_body, else the kernel of DESIGN 3.26
-    void run(int n, const SimGroundJointArgs & ja, const double * body = nullptr, const SimTerrainDev * terr = nullptr)
+    // `pts` non-null: the body-point kernels of DESIGN 3.29, always at 32 rows, on the terrain or on the plane
+    void run(int n, const SimGroundJointArgs & ja, const double * body = nullptr, const SimTerrainDev * terr = nullptr, const SimPointsDev * pts = nullptr)
     {
-      if (terr != nullptr)
+      if (pts != nullptr)
+      {
+        SimGroundPointsArgs pa;
+        pa.t.b.j = ja;
+        pa.t.b.body = body;
+        pa.t.t = terr != nullptr ? *terr : SimTerrainDev{nullptr, nullptr, nullptr, 0, 0, 0, 0.0, nullptr, nullptr};
+        pa.p = *pts;
+        if (terr != nullptr)
+          launch<SimGroundPointsArgs, sim_ground_points_terrain_rt_body<32>, 64, 1, 0>(n, g.sim.stream, pa);
+        else
+          launch<SimGroundPointsArgs, sim_ground_points_rt_body<32>, 64, 1, 0>(n, g.sim.stream, pa);
+      }
+      else if (terr != nullptr)
       {
         SimGroundTerrainArgs ta;
         ta.b.j = ja;
@@ -788,7 +1038,7 @@ namespace smpc
     // `env` and `ws` may be null or inactive: the handle's uniform ground, no push; `sweeps` sweeps from zero.  Before set_model every
     // array is null and stops = 0: the inert model (a handle with body parameters and no joint model steps through here).
     void step_device(double * X_dev, const double * tau_dev, double dt, const RobotSimGroundEnv * env, RobotSimGroundWs * ws, const double * body = nullptr,
-                     const SimTerrainDev * terr = nullptr)
+                     const SimTerrainDev * terr = nullptr, const SimPointsDev * pts = nullptr)
     {
       RobotSimRt & sim = g.sim;
       set_device(sim.device_id);
@@ -827,7 +1077,7 @@ namespace smpc
       ja.rows_out = rows;
       ja.lams_out = lams;
       ja.dropped_out = dropped;
-      run(sim.B, ja, body, terr);
+      run(sim.B, ja, body, terr, pts);
     }
     void read_last(double * tau_out, int * rows_out, double * lams_out, int * dropped_out)
     {
@@ -857,7 +1107,7 @@ namespace smpc
                   const SimGroundWsSettings & st, const double * lam0_h, const smpc_joint_model_settings * m, const double * tab_lo, const double * tab_hi,
                   double * v_out, double * a_out, double * lam_out, double * lamc_out, double * gap_out, unsigned * con_out, int * sweeps_out, double * resid_out,
                   double * tau_applied_out, int * rows_out, double * lams_out, int * dropped_out, const double * body_dev = nullptr,
-                  const SimTerrainDev * terr = nullptr)
+                  const SimTerrainDev * terr = nullptr, const SimPointsDev * pts = nullptr)
     {
       if (n < 1)
         throw InvalidCall("n must be positive");
@@ -973,7 +1223,7 @@ namespace smpc
       ja.rows_out = hRows;
       ja.lams_out = hLamS;
       ja.dropped_out = hDrop;
-      run(n, ja, body_dev, terr);
+      run(n, ja, body_dev, terr, pts);
       if (v_out)
         d2h(v_out, hV, (size_t)n * sz.nv * sizeof(double), stream);
       if (a_out)
@@ -1240,6 +1490,166 @@ namespace smpc
       if (heights_out)
         d2h(heights_out, sH, sim_terrain_hlast_bytes(n, g.gz.npts), sim.stream);
       stream_sync(sim.stream);
+    }
+  };
+
+  // ---- host: the body points of one simulator handle's ground (a sibling of RobotSimGroundTerrain, whose device view
+  // RobotSimGroundJoint::step_device and dynamics take).  `active` between set(settings with n > 0) and set(null or n = 0): while it is,
+  // the handle's ground steps launch a body-point kernel.  The staging of the host-buffer solve never touches the handle's own arrays. ----
+  struct RobotSimGroundPoints
+  {
+    struct Arrays
+    {
+      int * joint = nullptr;             // [16]
+      double * offset = nullptr;         // [16][3]
+      int * slots = nullptr;             // [n][8]
+      double * lam = nullptr;            // [n][8][3]
+      double * gap = nullptr;            // [n][16]
+      int * dropped = nullptr;           // [n]
+      unsigned char * touch = nullptr;   // [n]
+      void release()
+      {
+        dev_free(joint);
+        dev_free(offset);
+        dev_free(slots);
+        dev_free(lam);
+        dev_free(gap);
+        dev_free(dropped);
+        dev_free(touch);
+        *this = Arrays();
+      }
+    };
+    RobotSimGround & g;
+    bool active = false;
+    int n = 0;
+    double band = SIM_POINTS_DEFAULT_BAND;
+    Arrays own; // the handle's points and the read-outs of its last step, [B]
+    Arrays st;  // host-buffer form: [cap], grown on demand
+    int cap = 0;
+
+    explicit RobotSimGroundPoints(RobotSimGround & ground) : g(ground) {}
+    RobotSimGroundPoints(const RobotSimGroundPoints &) = delete;
+    RobotSimGroundPoints & operator=(const RobotSimGroundPoints &) = delete;
+    ~RobotSimGroundPoints()
+    {
+      own.release();
+      st.release();
+    }
+    static void allocate(Arrays & a, int count)
+    {
+      AllocScope scope; // (a failing allocation releases the ones before it; the pointers are kept only once all have succeeded)
+      Arrays t;
+      t.joint = (int *)dev_alloc(sim_points_joint_bytes());
+      t.offset = (double *)dev_alloc(sim_points_offset_bytes());
+      t.slots = (int *)dev_alloc(sim_points_slots_bytes(count));
+      t.lam = (double *)dev_alloc(sim_points_lam_bytes(count));
+      t.gap = (double *)dev_alloc(sim_points_gap_bytes(count));
+      t.dropped = (int *)dev_alloc(sim_points_dropped_bytes(count));
+      t.touch = (unsigned char *)dev_alloc(sim_points_touch_bytes(count));
+      scope.commit();
+      a = t;
+    }
+    static void upload(const Arrays & a, const smpc_body_points_settings * s, stream_t stream)
+    {
+      int hj[SIM_POINTS_MAX];
+      double ho[SIM_POINTS_MAX * 3];
+      for (int k = 0; k < SIM_POINTS_MAX; k++)
+      {
+        hj[k] = k < s->n ? s->joint[k] : 0;
+        for (int i = 0; i < 3; i++)
+          ho[k * 3 + i] = k < s->n ? s->offset[k][i] : 0.0;
+      }
+      h2d(a.joint, hj, sizeof(hj), stream);
+      h2d(a.offset, ho, sizeof(ho), stream);
+      stream_sync(stream); // (the two host arrays leave scope)
+    }
+    static SimPointsDev view_of(const Arrays & a, int n, double band)
+    {
+      SimPointsDev d;
+      d.joint = a.joint;
+      d.offset = a.offset;
+      d.n = n;
+      d.band = band;
+      d.slots_out = a.slots;
+      d.lam_out = a.lam;
+      d.gap_out = a.gap;
+      d.dropped_out = a.dropped;
+      d.touch_out = a.touch;
+      return d;
+    }
+    void zero(const Arrays & a, int count)
+    {
+      stream_t stream = g.sim.stream;
+      dev_zero(a.slots, sim_points_slots_bytes(count), stream);
+      dev_zero(a.lam, sim_points_lam_bytes(count), stream);
+      dev_zero(a.gap, sim_points_gap_bytes(count), stream);
+      dev_zero(a.dropped, sim_points_dropped_bytes(count), stream);
+      dev_zero(a.touch, sim_points_touch_bytes(count), stream);
+    }
+    // (the caller has run sim_points_admission_error) the settings to the device; null or n = 0 clears: the handle launches what it launched before
+    void set(const smpc_body_points_settings * s)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      sim.wait(); // (a step in flight still reads the arrays)
+      if (!s || s->n == 0)
+      {
+        active = false;
+        return;
+      }
+      if (!own.joint)
+        allocate(own, sim.B);
+      upload(own, s, sim.stream);
+      zero(own, sim.B);
+      stream_sync(sim.stream);
+      n = s->n;
+      band = sim_points_band(s->band);
+      active = true;
+    }
+    // the device view of the handle's points for a step
+    SimPointsDev view() const { return view_of(own, n, band); }
+    static void read_from(const Arrays & a, int count, stream_t stream, int * slots_out, double * lam_out, double * gap_out, int * dropped_out,
+                          unsigned char * touch_out)
+    {
+      if (slots_out)
+        d2h(slots_out, a.slots, sim_points_slots_bytes(count), stream);
+      if (lam_out)
+        d2h(lam_out, a.lam, sim_points_lam_bytes(count), stream);
+      if (gap_out)
+        d2h(gap_out, a.gap, sim_points_gap_bytes(count), stream);
+      if (dropped_out)
+        d2h(dropped_out, a.dropped, sim_points_dropped_bytes(count), stream);
+      if (touch_out)
+        d2h(touch_out, a.touch, sim_points_touch_bytes(count), stream);
+      stream_sync(stream);
+    }
+    void read_last(int * slots_out, double * lam_out, double * gap_out, int * dropped_out, unsigned char * touch_out)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      read_from(own, sim.B, sim.stream, slots_out, lam_out, gap_out, dropped_out, touch_out);
+    }
+    // the settings of a host-buffer solve of `count` states (s->n > 0) to the staging arrays, on the handle's stream; the device view for
+    // RobotSimGroundJoint::dynamics
+    SimPointsDev stage(int count, const smpc_body_points_settings * s)
+    {
+      RobotSimRt & sim = g.sim;
+      set_device(sim.device_id);
+      if (count > cap)
+      {
+        stream_sync(sim.stream);
+        st.release();
+        cap = 0;
+        allocate(st, count);
+        cap = count;
+      }
+      upload(st, s, sim.stream);
+      return view_of(st, s->n, sim_points_band(s->band));
+    }
+    // (after the solve) the five read-outs of the staging arrays
+    void read_staged(int count, int * slots_out, double * lam_out, double * gap_out, int * dropped_out, unsigned char * touch_out)
+    {
+      read_from(st, count, g.sim.stream, slots_out, lam_out, gap_out, dropped_out, touch_out);
     }
   };
 } // namespace smpc

@@ -192,6 +192,15 @@ class TerrainSettingsC(C.Structure):  # smpc_terrain_settings
     ]
 
 
+class BodyPointsSettingsC(C.Structure):  # smpc_body_points_settings
+    _fields_ = [
+        ("n", C.c_int32),
+        ("joint", C.c_int32 * 16),
+        ("offset", (C.c_double * 3) * 16),
+        ("band", C.c_double),
+    ]
+
+
 # every symbol declared in include/smpc.h
 SYMBOLS = [
     "smpc_builtin_robot", "smpc_last_error", "smpc_device_count", "smpc_create", "smpc_create_centroidal", "smpc_create_fulldynamics", "smpc_get_contact_forces", "smpc_destroy", "smpc_get_dims",
@@ -212,6 +221,7 @@ SYMBOLS = [
     "smpc_robot_sim_set_joint_model", "smpc_robot_sim_get_joint_last", "smpc_robot_sim_read_joint_last", "smpc_robot_sim_ground_joint_dynamics",
     "smpc_robot_sim_set_body_params", "smpc_robot_sim_read_body_params", "smpc_robot_sim_get_body_params", "smpc_robot_sim_ground_body_dynamics",
     "smpc_robot_sim_set_terrain", "smpc_robot_sim_get_terrain", "smpc_robot_sim_read_terrain_last", "smpc_robot_sim_get_terrain_last", "smpc_robot_sim_ground_terrain_dynamics",
+    "smpc_robot_sim_set_body_points", "smpc_robot_sim_get_body_points_last", "smpc_robot_sim_read_body_points_last", "smpc_robot_sim_ground_points_dynamics",
 ]
 
 
@@ -384,6 +394,12 @@ class SmpcLib:
         L.smpc_robot_sim_ground_terrain_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, C.POINTER(TerrainSettingsC), vp, vp, C.c_int,
                                                              C.POINTER(GroundSolverSettingsC), vp, C.POINTER(JointModelSettingsC), vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                              vp, vp, vp, vp, vp, vp]
+        L.smpc_robot_sim_set_body_points.argtypes = [vp, C.POINTER(BodyPointsSettingsC)]
+        L.smpc_robot_sim_get_body_points_last.argtypes = [vp] + [C.POINTER(vp)] * 5
+        L.smpc_robot_sim_read_body_points_last.argtypes = [vp] + [vp] * 5
+        L.smpc_robot_sim_ground_points_dynamics.argtypes = [vp, C.c_int, _dp, _dp, C.c_double, C.POINTER(TerrainSettingsC), vp, vp, vp, C.c_int,
+                                                            C.POINTER(GroundSolverSettingsC), vp, C.POINTER(JointModelSettingsC), vp,
+                                                            C.POINTER(BodyPointsSettingsC)] + [vp] * 19
 
     def check(self, code):
         if code < 0:
